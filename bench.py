@@ -20,6 +20,16 @@ re-evaluated every step, as sample_model does), one persistent
 faithful_chain_kernel launch per 1000-step chain; with its own roofline and
 CPU baseline (oracle/ref_torch.py, bit-identical to the reference).
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) sets up, warms up, times
+the N steps and prints the JSON line: the headline figure, ms_per_step and the
+roofline object computed from the same timed steps.  More than T steps run as
+whole chains, each restarted from x_T.  --dump-outputs DIR then writes the
+sampler state the last timed step left (the array sample_model returns) to
+DIR/x.npy; inputs and noise are seeded, so two builds can be compared output
+for output.  Every measurement that takes runs of its own -- the CPU
+baselines, the per-kernel figures, the other BASELINE configs, training, KDE,
+extra.reference_model -- runs only with --full.
+
 Extra objects on the JSON line:
   roofline      the dominant kernel of the headline: the U-Net's fp32-MFMA
                 implicit-GEMM conv kernels (conv_kernel<...>, ~93 % of the
@@ -68,6 +78,11 @@ PEAK_BF16_TFLOPS = 2500.0    # dense bf16 MFMA
 PEAK_HBM_GBS = 8000.0
 
 
+# the measurements beside the headline, each behind --full and its own --no-* switch
+SECONDARY_LEGS = ("cpu_baseline", "conv_kernels", "u3", "ensemble", "u5", "hbm_kernels", "unet_train",
+                  "kde", "reference", "evaluation")
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -112,7 +127,20 @@ def parse():
     ap.add_argument("--no-steps-schedule", action="store_true",
                     help="skip the secondary per-step-schedule timing")
     ap.add_argument("--roofline-reps", type=int, default=200)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (CPU baselines, per-kernel rooflines, "
+                         "the other BASELINE configs, training, KDE, the reference model); the --no-* "
+                         "options select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sampler state the last timed step left "
+                         "(what a caller of the sampler receives) to DIR/x.npy as float32")
+    a = ap.parse_args()
+    if not a.full:
+        # a plain run measures the headline only: set-up, warm-up, the timed
+        # steps, the optional dump and the result line
+        for leg in SECONDARY_LEGS:
+            setattr(a, "no_" + leg, True)
+    return a
 
 
 def setup_dist():
@@ -898,18 +926,21 @@ def cpu_unet_train_baseline(name, seconds, B, T=1000, threads=None):
 
 
 def time_unet(model, cond, B, steps, warmup, T, seed, offset, world, dev, shared=False):
-    """One UNetSamplerPlan of `steps` reverse steps from t = T-1.  Warmup runs
-    `warmup` steps through the SAME plan (so its graphs are uploaded before
-    timing), x is reset to x_T, then the timed replay sits between barrier +
-    synchronize on both sides; HIP events on the launching stream beside the
-    host clock.  Returns (host seconds max over ranks, event seconds, plan)."""
+    """One UNetSamplerPlan of `steps` reverse steps from t = T-1 (more than T
+    steps: whole T-step chains, each restarted from x_T, then one partial
+    chain).  Warmup runs `warmup` steps through the SAME plan (so its graphs
+    are uploaded before timing), x is reset to x_T, then the timed replay sits
+    between barrier + synchronize on both sides; HIP events on the launching
+    stream beside the host clock.  Returns (host seconds max over ranks, event
+    seconds, plan)."""
     sched = ertdiff.get_diffusion_schedule(T, device=dev)
     x_T = ertdiff.philox_normal(B, model.param_dim, T, 1, seed, offset, dev)
-    plan = ertdiff.UNetSamplerPlan(model, cond, T, *sched, t_first=T - 1, n_run=steps, seed=seed,
+    n_run = min(steps, T)
+    plan = ertdiff.UNetSamplerPlan(model, cond, T, *sched, t_first=T - 1, n_run=n_run, seed=seed,
                                    member_offset=offset, B=B, shared_condition=shared)
     left = max(1, warmup)
     while left > 0:
-        n = min(left, steps)
+        n = min(left, n_run)
         plan.x.copy_(x_T)
         plan.launch(n_steps=n)
         left -= n
@@ -921,7 +952,13 @@ def time_unet(model, cond, B, steps, warmup, T, seed, offset, world, dev, shared
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record(stream)
-    plan.launch(stream)
+    done = 0
+    while done < steps:
+        n = min(n_run, steps - done)
+        if done:
+            plan.x.copy_(x_T)
+        plan.launch(stream, n_steps=n)
+        done += n
     e1.record(stream)
     torch.cuda.synchronize(dev)
     barrier(world)
@@ -1096,6 +1133,11 @@ def main():
                                  f"convolution counted per layer, = torch FlopCounter) x {B} members",
             "algorithmic_tflops": round(achieved, 3),
             "algorithmic_frac": round(achieved / PEAK_FP32_TFLOPS, 4)}
+    if a.dump_outputs:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        name = "x.npy" if world == 1 else f"x_rank{rank}.npy"
+        rows = max(1, min(B, (64 << 20) // (4 * world * model.param_dim)))   # at most 64 MB in all
+        np.save(os.path.join(a.dump_outputs, name), timed.x[:rows].cpu().numpy().astype(np.float32))
     extra = {"unet_step_tflops_all": round(flops["total"] * B / step_s / 1e12 * world, 2),
              "unet_flop_per_sample_step": flops, "member_steps_per_s": round(value * B, 1)}
     cpu = None
@@ -1191,7 +1233,9 @@ def main():
                                    f"{', mid attention' if spec['attn'] else ''}), T={T}, batch {B}, "
                                    f"fp32 (BASELINE configs[1]; build-defined, SURVEY 8a')",
                        "global_batch": B * world, "members_per_gpu": B, "T": T,
-                       "steps_timed": f"t = {T - 1} .. {T - a.steps}",
+                       "steps_timed": f"t = {T - 1} .. {T - a.steps}" if a.steps <= T else
+                                      f"{a.steps} steps as chains t = {T - 1} .. 0, each from x_T "
+                                      f"(the last one {a.steps % T or T} steps)",
                        "precision": "fp32", "parallelism": f"dp{world} (member shards)"},
             "roofline": roof, "cpu_baseline": cpu, "extra": extra,
         }

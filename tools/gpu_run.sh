@@ -13,6 +13,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   rc=$?; tail -2 gpurun_out/smoke.log; echo "[smoke] rc=$rc"; [ $rc -ne 0 ] && exit $rc
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"   # every secondary measurement, as the round-end line records
   timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
   rc=$?; echo "[bench] rc=$rc"; grep '^{' gpurun_out/bench.log | cut -c1-600; [ $rc -ne 0 ] && tail -20 gpurun_out/bench.log
   exit $rc
