@@ -18,6 +18,10 @@ from .postproc import compact, postprocess, sample_realisations
 from .unet import ConditionalUNet, UNetSamplerPlan, sample_unet
 from .unet_train import UNetTrainPlan, unet_train_backward, unet_train_forward, unet_train_step
 from .kde import ensemble_mode, kde_mode, mode_kde_calculation
+from .stats import (WSSE_metric, accuracy_score, avg_prop_indicator_function, coverage_counts,
+                    coverage_curve, coverage_from_counts, ensemble_moments, ensemble_percentile,
+                    ensemble_summary, goodness_score, interval_fractions,
+                    parameter_uncertainty_metrics, preccision_score, uncertainty_metrics, wsse)
 
 __all__ = [
     "ConditionalDiffusionModel", "get_timestep_embedding", "get_diffusion_schedule", "q_sample",
@@ -28,4 +32,8 @@ __all__ = [
     "sample_ensemble", "member_range", "sample_conditions", "sample_conditions_sharded", "postprocess", "sample_realisations", "compact",
     "ConditionalUNet", "UNetSamplerPlan", "sample_unet", "kde_mode", "ensemble_mode",
     "mode_kde_calculation", "unet_train_step", "UNetTrainPlan", "unet_train_forward", "unet_train_backward",
+    "ensemble_percentile", "ensemble_moments", "ensemble_summary", "coverage_curve", "coverage_counts",
+    "coverage_from_counts", "interval_fractions", "parameter_uncertainty_metrics", "wsse", "WSSE_metric",
+    "avg_prop_indicator_function", "accuracy_score", "preccision_score", "goodness_score",
+    "uncertainty_metrics",
 ]

@@ -177,6 +177,10 @@ SIGNATURES = {
     "ertd_kde_mode": (_I, [_VP, _I, ctypes.c_longlong, ctypes.c_longlong, _I, _I, ctypes.c_double,
                            ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
     "ertd_minmax_f64": (_I, [_VP, ctypes.c_longlong, _VP, _VP, _VP]),
+    "ertd_ens_percentile": (_I, [_VP, _I, _I, _LL, _LL, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "ertd_ens_moments": (_I, [_VP, _I, _I, _LL, _LL, _VP, _I, _VP, _VP, _VP]),
+    "ertd_coverage": (_I, [_VP, _VP, _I, _I, _LL, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "ertd_wsse": (_I, [_VP, _VP, _I, _I, _LL, _I, ctypes.c_double, ctypes.c_double, _VP, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

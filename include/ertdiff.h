@@ -635,6 +635,55 @@ int ertd_kde_mode(const double* x, int n, long long cells, long long ld, int gri
 #define ERTD_MINMAX_BLOCKS 1024
 int ertd_minmax_f64(const double* x, long long count, double* work, double* out2, void* stream);
 
+/* ---- Ensemble order statistics, coverage, moments, WSSE (csrc/ensstats.hip) ----
+ * Replaces the host numpy the reference runs on the sampler's and the
+ * simulator's ensembles: ERT_Conditional_Diffusion.py:867-876 (per-cell mean,
+ * std, variance, P25/P50/P75), :1121-1132 and :1191-1205 (60 np.percentile
+ * calls, the coverage indicator and its mean per level) and :767-787 (WSSE).
+ * Every entry point takes float32 or float64 input (dtype) and computes in
+ * float64.  x: (n, ld) row-major on the device, cell c = column c < cells
+ * (the layout of the KDE entry point above).
+ * valid_rows (optional): uint8 (n, cells / rows_per_valid), the mask that
+ * postprocessing writes -- one entry covers the rows_per_valid adjacent
+ * columns of a test sample; cells must be a multiple of rows_per_valid.  A
+ * column's used samples are the m rows whose entry is set (m = n without a
+ * mask).                                                                    */
+#define ERTD_F32 0
+#define ERTD_F64 1
+/* Percentiles of every column, bit for bit np.percentile(x, 100 q, axis=0)
+ * (method "linear"): with s the sorted used samples, vi = (m-1) q[k],
+ * lo = floor(vi), hi = min(lo+1, m-1), t = vi - lo, d = s[hi] - s[lo] formed
+ * in the input's dtype, out[k, c] = t < 0.5 ? s[lo] + d t : s[hi] - d (1-t)
+ * in float64.  q: nq float64 fractions in [0, 1] on the device; out: (nq,
+ * cells) float64; n_eff (cells, optional) receives m.  A column with m = 0,
+ * or with a NaN among its used samples, yields NaN.  Requires
+ * 1 <= n <= 16384 (one workgroup sorts a whole column in LDS).              */
+int ertd_ens_percentile(const void* x, int dtype, int n, long long cells, long long ld,
+                        const unsigned char* valid_rows, int rows_per_valid, const double* q,
+                        int nq, double* out, int* n_eff, void* stream);
+/* Mean and population variance (ddof = 0) of every column, two passes:
+ * mean[c] = sum(x) / m, var[c] = sum((x - mean)^2) / m, each (cells) float64.
+ * m = 0 yields NaN.  n >= 1.                                                */
+int ertd_ens_moments(const void* x, int dtype, int n, long long cells, long long ld,
+                     const unsigned char* valid_rows, int rows_per_valid, double* mean,
+                     double* var, void* stream);
+/* The calibration loop in one launch.  ens: (S, N, P); truth: (N, P), same
+ * dtype; q_low, q_upp: K float64 fractions (device), the bounds of K central
+ * intervals.  Per column (i, p) the two bounds are the percentiles above and
+ * counts[k, p] += (low < truth) & (truth <= upp), compared in float64;
+ * cols[p] += 1 for every column with m >= 1 (columns with m = 0 enter
+ * neither).  counts (K, P) and cols (P) are int32 and are zeroed by the call;
+ * integer accumulation, so the result is deterministic and the counts of
+ * disjoint slices of N add up.  valid_rows (optional): (S, N).
+ * Requires 1 <= S <= 16384 and (K + 1) P <= 4096.                           */
+int ertd_coverage(const void* ens, const void* truth, int dtype, int S, long long N, int P,
+                  const unsigned char* valid_rows, const double* q_low, const double* q_upp, int K,
+                  int* counts, int* cols, void* stream);
+/* WSSE per realisation and survey: pred (n, M, E), obs (M, E), same dtype;
+ * out[s, e] = mean over m of (pred - obs)^2 / (A |obs| + B)^2, (n, E) float64. */
+int ertd_wsse(const void* pred, const void* obs, int dtype, int n, long long M, int E, double A,
+              double B, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
