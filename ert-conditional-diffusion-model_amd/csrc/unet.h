@@ -92,11 +92,11 @@ struct ConvArgs {
   int split;             // bf16 kernels: 1 = split-bf16 operands (hi + lo planes: weights
                          // packed with split = true, images of conv_bf16_image_bytes(.., true))
   GnFold fold;           // fp32 Winograd F(4x4) kernels with gnp: the next GroupNorm's finalize
-                         // (fold.cnt null: none; conv_gn_fold_ok says where it is taken)
+                         // (fold.cnt null: none; WinoRoute::fold_ok says where it is taken)
   unsigned* zero_words;  // conv_in: zero these zero_n words (the fold counters of the walk)
   int zero_n;
   GnPartArgs gnc;        // fp32 Winograd F(4x4) consumers (gnc.pa non-null): the input's
-                         // GroupNorm finalize in the conv's own prologue (conv_gn_consume_ok):
+                         // GroupNorm finalize in the conv's own prologue (wino_gnc_ok):
                          // the {scale, shift} of the sample the workgroup runs are merged from
                          // these partials into LDS -- no finalize launch, gn unused
 };
@@ -112,21 +112,38 @@ struct ConvArgs {
 hipError_t launch_gn_finalize(const GnPartArgs& a, int B, hipStream_t s);
 // x (B, C, HW) -> (B, C, np) partials of 256 pixels: HW == 256 np
 hipError_t launch_gn_partials(const float* x, int C, int HW, int np, float2* out, int B, hipStream_t s);
-// parts per (sample, channel) the kernel launch_conv would dispatch emits into
-// ConvArgs::gnp (0 = none: the Winograd layers without a K split do)
-int conv_gn_parts(int ks, int mode, int act, const ConvArgs& a, int B);
+// ---- the route of an fp32 3x3 conv (unet_conv_wino.hip) ---------------------------
+// Everything the dispatch decides about one layer, decided once: the sizing
+// queries, the layer walk and the launchers all read this value.
+struct WinoRoute {
+  enum Kernel { NONE,     // not a Winograd layer: the direct / sub-pixel kernels
+                F2,       // F(2x2,3x3) (unet_conv_wino.hip)
+                F4,       // F(4x4,3x3), weights in LDS (unet_conv_wino4.hip)
+                F4S,      // F(4x4,3x3), weights in registers (unet_conv_wino4s.hip)
+                F4S_UP    // the same kernel on the nearest-x2 source (the Upsample conv)
+  } kernel = NONE;
+  int ksplit = 1;         // 2: K (input channels) in two halves, the second into
+                          // ConvArgs::ksplit_buf (kbuf_floats floats), summed by a pass
+  size_t kbuf_floats = 0;
+  int items = 0, grid = 0;   // tile items (both halves of a split) and workgroups of the launch
+  int gn_parts = 0;       // GroupNorm partials per (sample, channel) the epilogue emits (0: none)
+  bool fold_ok = false;   // the kernel takes ConvArgs::fold (diagnostic builds)
+  int fold_target = 0;    // F4S / F4S_UP: items per sample = the fold's arrivals (GnFold::target)
+  int pack_kind = ERTD_PACK_DIRECT;   // the weight packing the launch reads (ERTD_PACK_*)
+};
+// mode / act as launch_conv; Wo = the OUTPUT width; have_*_pack: the F(2x2) /
+// F(4x4) packing exists (ConvArgs::wpk_wino / wpk_wino4); cus = device_cu_count()
+WinoRoute wino_route(int mode, int act, int Cin, int Ca, int Cout, int Wo, int B, bool have_f2_pack,
+                     bool have_f4_pack, int cus);
+// true where the routed kernel takes ConvArgs::gnc = g (the input's GroupNorm
+// finalize in the conv's prologue): F4S without a K split whose finalize jobs
+// and per-item tables fit the workgroup (unet_conv_wino4s.hip)
+bool wino_gnc_ok(const WinoRoute& r, int Cin, int Wo, const GnPartArgs& g);
+// parts per (sample, channel) the kernel launch_conv dispatches emits into
+// ConvArgs::gnp (0 = none): conv_in's, else the route's
+int conv_gn_parts(int ks, int mode, int act, const ConvArgs& a, const WinoRoute& r);
 // the same for the bf16 / split-bf16 convs (unet_conv_bf16.hip)
 int conv_bf16_gn_parts(int ks, int mode, int act, const ConvArgs& a, int B);
-int wino_gn_parts(const ConvArgs& a, int B);
-// true where the kernel launch_conv would dispatch (fp32) takes ConvArgs::fold:
-// the Winograd F(4x4) register-weight kernel without a K split
-bool conv_gn_fold_ok(int ks, int mode, int act, const ConvArgs& a, int B);
-// its MFMA-wave arrivals per sample (GnFold::target)
-int conv_gn_fold_target(const ConvArgs& a, int B);
-// true where the kernel launch_conv would dispatch (fp32) takes ConvArgs::gnc:
-// the Winograd F(4x4) register-weight kernel without a K split whose items
-// divide evenly over its workgroups with each workgroup's items in one sample
-bool conv_gn_consume_ok(int ks, int mode, int act, const ConvArgs& a, int B);
 
 // sum over the 16 lanes of a DPP row (lanes 16r .. 16r+15), the same bits in
 // every lane of the row (fixed pairing: quad swaps, then the half-row and row
@@ -373,40 +390,20 @@ hipError_t launch_conv_out(int act, const ConvArgs& a, int B, int pk, hipStream_
 // one thread per output pixel, every output channel's 9-tap fp32 fma chain
 bool conv_in_ok(const ConvArgs& a, int ks, int mode, int act);
 hipError_t launch_conv_in(const ConvArgs& a, int B, int pk, hipStream_t s);
-// fp32 3x3 stride-1 convs by Winograd F(2x2,3x3) (unet_conv_wino.hip): eligible
-// shapes (Cin, Ca multiples of 8, Cout of 64, W in 16..128; ERTD_UNET_WINO=0
-// disables), the U = G g G^T packing (0 floats: shape not eligible), launch
-hipError_t launch_conv_wino(int act, const ConvArgs& a, int B, hipStream_t s);
-bool conv_wino_ok(int cin, int ca, int cout, int wo);
-// a Winograd layer with this geometry splits its K when given ConvArgs::ksplit_buf
-bool wino_ksplit_wanted(int cin, int cout, int wo, int B);
+// the routed fp32 3x3 Winograd kernels (r.kernel != NONE, r from wino_route for
+// this launch's geometry; ConvArgs::ksplit_buf set where r.ksplit == 2)
+hipError_t launch_conv_wino(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r);
+hipError_t launch_conv_wino4(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r);
+hipError_t launch_conv_wino4s(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r);
+// Winograd packings U = G g G^T (0 floats: shape not eligible): F(2x2) for Cin a
+// multiple of 8, F(4x4) of 4, Cout of 64
 size_t conv_packed_floats_wino(int cin, int cout);
-// Winograd F(4x4,3x3) (unet_conv_wino4.hip): Cin, Ca multiples of 4, Cout of 64,
-// W in {32, 64, 128} (16 with an even batch); ERTD_UNET_WINO=2 keeps F(2x2) everywhere.  A Winograd
-// launch (launch_conv_wino) takes it when wino4_ok and ConvArgs::wpk_wino4 is set.
-bool wino4_ok(int cin, int ca, int cout, int wo, int B);
-bool wino_dispatchable(const ConvArgs& a, int B);
 size_t conv_packed_floats_wino4(int cin, int cout);
 hipError_t launch_pack_conv_wino4(const float* w, int cin, int cout, float* dst, hipStream_t s,
                                   bool flipT = false);
-hipError_t launch_conv_wino4(int act, const ConvArgs& a, int B, hipStream_t s, int cus);
-int wino4_tile_items(int cout, int wo, int B);
-// the F(4x4) register-weight kernel splits its K (given ConvArgs::ksplit_buf)
-bool wino4s_ksplit(int cin, int cout, int wo, int B);
-bool wino4_ksplit(int cin, int cout, int wo, int B);
-// F(4x4) with register-resident weights (unet_conv_wino4s.hip): items of 64 co x
-// 16 tiles (the 16x16 level fills the CUs at B = 64 without a K split); same
-// wpk_wino4 packing; Cin a multiple of 8, Ca even, W in {16, 32, 64}.  wino4_ok
-// is true where wino4s_ok is, and launch_conv_wino then dispatches it.
-bool wino4s_ok(int cin, int ca, int cout, int wo, int B);
-int wino4s_items(int cout, int wo, int B);
-bool wino4s_fold_ok(const ConvArgs& a, bool up, int B);
-bool wino4s_gnc_ok(const ConvArgs& a, int B);
-int wino4s_fold_target(const ConvArgs& a);
-// the same kernel for the fp32 Upsample conv (MODE_UP, no activation; wo = the
-// OUTPUT width): conv3x3 of the nearest-x2 source through the F(4x4) packing
-bool wino4s_up_ok(int cin, int ca, int cout, int wo, int B);
-hipError_t launch_conv_wino4s(int act, const ConvArgs& a, int B, hipStream_t s, int cus);
+// schedule knobs of the F(4x4) register-weight kernel that the route and its
+// launcher both read (unet_conv_wino.hip)
+int wino4s_xs();
 hipError_t launch_add_inplace(float* out, const float* part, size_t n, hipStream_t s);
 // flipT: w is a forward conv's (cin, cout, 3, 3) weight; pack the input-gradient
 // conv's weight W'[co][ci] = W[ci][co] spatially flipped (training)

@@ -183,10 +183,10 @@ Layout layout(const ertd_unet_config* c) {
                           : conv_packed_floats(p.shape[1], p.shape[0], p.shape[2])));
     else o += a64(p.numel());
     // fp32 ResBlock 3x3 convs also get the Winograd F(2x2,3x3) packing
-    // (dispatch picks it when conv_wino_ok; ERTD_UNET_WINO=0 keeps the direct one)
+    // (wino_route picks the kernel; ERTD_UNET_WINO=0 keeps the direct one)
     if (c->precision == ERTD_PREC_FP32 && p.shape.size() == 4 && p.shape[2] == 3 &&
         ends_with(p.name, ".upsample.weight") && conv_packed_floats_wino4(p.shape[1], p.shape[0]) > 0) {
-      // ... and the Upsample convs the F(4x4) packing (wino4s_up_ok dispatch)
+      // ... and the Upsample convs the F(4x4) packing (the route's F4S_UP)
       L.offw4[p.name] = o;
       o += a64(conv_packed_floats_wino4(p.shape[1], p.shape[0]));
     }
@@ -277,7 +277,7 @@ struct Walk {
   float2* next_gnbuf() const { return gnbuf == gnb[0] ? gnb[1] : gnb[0]; }
   void plan_folds() {
     Walk d{c, L, pk, nullptr, 0, B, nullptr, true};
-    d.fold_cnt = reinterpret_cast<unsigned*>(16);   // plan as the real walk (never dereferenced)
+    d.fold_cnt = fold_cnt;   // plan as the real walk (a dry walk never dereferences it)
     d.unet(nullptr, nullptr, nullptr);
     plan_evs = d.evs;
     fold_at.assign(plan_evs.size(), -1);
@@ -309,7 +309,7 @@ struct Walk {
   }
 
   // fp32: a GroupNorm finalize not yet launched -- the next conv either takes
-  // it into its prologue (conv_gn_consume_ok) or launches it first
+  // it into its prologue (wino_gnc_ok) or launches it first
   GnPartArgs pend_fin{};
   bool has_pend_fin = false;
   void flush_fin() {
@@ -411,45 +411,42 @@ struct Walk {
     if (mode == MODE_S2) { Ho = Hs / 2; Wo = Ws / 2; }
     if (mode == MODE_UP) { Ho = Hs * 2; Wo = Ws * 2; }
     if (!out) out = alloc((size_t)B * Cout * Ho * Wo);
-    // fp32 Winograd layers with fewer tile items than CUs split their K
-    const bool want_split = c->precision == ERTD_PREC_FP32 && ks == 3 && mode == MODE_S1 &&
-                            (L->offw.count(n + ".weight") || L->offw4.count(n + ".weight")) &&
-                            conv_wino_ok(Cin, Ca, Cout, Wo) && wino_ksplit_wanted(Cin, Cout, Wo, B);
-    float* kbuf = want_split ? alloc((size_t)B * Cout * Ho * Wo) : nullptr;
+    const bool fp32 = c->precision == ERTD_PREC_FP32;
+    // fp32 3x3: the kernel this layer runs on and everything that follows from it
+    const WinoRoute route = fp32 && ks == 3
+                                ? wino_route(mode, act, Cin, Ca, Cout, Wo, B, L->offw.count(n + ".weight") > 0,
+                                             L->offw4.count(n + ".weight") > 0, device_cu_count())
+                                : WinoRoute{};
+    // Winograd layers with fewer tile items than CUs split their K
+    float* kbuf = route.kbuf_floats ? alloc(route.kbuf_floats) : nullptr;
     // bf16 stride-1 convs stage a pre-transformed bf16 copy of their input
     float* bimg = nullptr;
     const bool split = c->precision == ERTD_PREC_BF16X3;
     if (bf_prec(c->precision) && ks == 3 && Cout > 1 &&
         ((mode == MODE_S1 && act != ACT_NONE) || (mode == MODE_UP && act == ACT_NONE)))
       bimg = alloc((conv_bf16_image_bytes(Ca + Cb, B, Ho, Wo, split) + 3) / 4);
-    // fp32: GroupNorm partials of the output, when the dispatched kernel emits
-    // them (the geometry-only part of the dispatch: sentinel pointers in dry runs)
+    // GroupNorm partials of the output, when the dispatched kernel emits them
     float2* gnp = nullptr;
     int gnp_np = 0;
-    ConvArgs q{};   // the dispatch geometry (sentinel pointers)
+    ConvArgs q{};   // the geometry conv_in_ok and the bf16 dispatch read
     q.Ca = Ca; q.Cb = Cb; q.Cin = Cin; q.Cout = Cout;
     q.Hs = Hs; q.Ws = Ws; q.Ho = Ho; q.Wo = Wo;
     q.ebias = ebias; q.res = res;
-    q.wpk_wino = L->offw.count(n + ".weight") ? reinterpret_cast<const float*>(16) : nullptr;
-    q.wpk_wino4 = L->offw4.count(n + ".weight") ? reinterpret_cast<const float*>(16) : nullptr;
-    q.ksplit_buf = want_split ? reinterpret_cast<float*>(16) : nullptr;
     if (gn_parts_on() && gn_out) {
       const int np = bf_prec(c->precision) ? conv_bf16_gn_parts(ks, mode, act, q, B)
-                                           : conv_gn_parts(ks, mode, act, q, B);
+                                           : conv_gn_parts(ks, mode, act, q, route);
       if (np > 0) {
         gnp = (float2*)alloc((size_t)B * Cout * np * 2);
         gnp_np = np;
         parts[out] = PartRec{gnp, np};
       }
     }
-    const bool fp32 = c->precision == ERTD_PREC_FP32;
     const bool zero_cnt = fp32 && fold_cnt && fold_env() && conv_in_ok(q, ks, mode, act);
     if (zero_cnt) cnt_zeroed = true;
     const int ev = (int)evs.size();
     {
       Ev e{false, false};
-      e.foldable = gnp && fp32 && fold_cnt && cnt_zeroed && fold_env() &&
-                   conv_gn_fold_ok(ks, mode, act, q, B);
+      e.foldable = gnp && fp32 && fold_cnt && cnt_zeroed && fold_env() && route.fold_ok;
       evs.push_back(e);
       ev_out.push_back(out);
       producer[out] = ev;
@@ -490,17 +487,15 @@ struct Walk {
       a.fold.g = GnPartArgs{gnp, gnp_np, Cout, rb.p, rb.np, g.Cb, g.HW, c->groups,
                             P(g.name + ".weight"), P(g.name + ".bias"), tgt, nullptr};
       a.fold.cnt = fold_cnt;
-      a.fold.target = conv_gn_fold_target(a, B);
+      a.fold.target = route.fold_target;
       a.fold.B = B;
       pfold = PendFold{fold_at[ev], tgt};
     }
     if (has_pend_fin) {
-      ConvArgs t = a;
-      t.gnc = pend_fin;
-      t.gnc.out = nullptr;
-      t.gn = nullptr;
-      if (act != ACT_NONE && a.gn == pend_fin.out && conv_gn_consume_ok(ks, mode, act, t, B)) {
-        a = t;
+      if (act != ACT_NONE && a.gn == pend_fin.out && wino_gnc_ok(route, Cin, Wo, pend_fin)) {
+        a.gnc = pend_fin;
+        a.gnc.out = nullptr;
+        a.gn = nullptr;
         has_pend_fin = false;
       } else {
         flush_fin();
@@ -858,6 +853,16 @@ bool conv2d_geom_ok(int cin, int cout, int ks, int precision, int B, int H, int 
          (precision == ERTD_PREC_FP32 || bf_prec(precision));
 }
 
+int conv2d_out_size(int H, int mode) { return mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H); }
+
+// the route ertd_conv2d takes: its workspace holds whichever Winograd packing
+// the shape admits (every other conv: no route, the direct packing)
+WinoRoute conv2d_route(int cin, int ca, int cout, int ks, int mode, int act, int precision, int B, int H) {
+  if (bf_prec(precision) || ks != 3) return WinoRoute{};
+  return wino_route(mode, act, cin, ca, cout, conv2d_out_size(H, mode), B, conv_packed_floats_wino(cin, cout) > 0,
+                    conv_packed_floats_wino4(cin, cout) > 0, device_cu_count());
+}
+
 Conv2dWs conv2d_ws(int cin, int ca, int cout, int ks, int precision, int B, int H, int mode, int act) {
   Conv2dWs w;
   const bool bf = bf_prec(precision), split = precision == ERTD_PREC_BF16X3;
@@ -869,11 +874,8 @@ Conv2dWs conv2d_ws(int cin, int ca, int cout, int ks, int precision, int B, int 
   if (!bf && ks == 3)
     f = a64(f) + std::max(conv_packed_floats_wino(cin, cout), conv_packed_floats_wino4(cin, cout));
   w.pack_floats = f;
-  const int Ho = mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H);
-  if (!bf && ks == 3 && mode == MODE_S1 && cout > 1 &&
-      (conv_packed_floats_wino(cin, cout) > 0 || conv_packed_floats_wino4(cin, cout) > 0) &&
-      conv_wino_ok(cin, ca, cout, Ho) && wino_ksplit_wanted(cin, cout, Ho, B))
-    w.kbuf_floats = (size_t)B * cout * Ho * Ho;
+  const int Ho = conv2d_out_size(H, mode);
+  w.kbuf_floats = conv2d_route(cin, ca, cout, ks, mode, act, precision, B, H).kbuf_floats;
   if (bf && ks == 3 && cout > 1 &&
       ((mode == MODE_S1 && act != ACT_NONE) || (mode == MODE_UP && act == ACT_NONE)))
     w.bimg_bytes = conv_bf16_image_bytes(cin, B, Ho, Ho, split);
@@ -895,17 +897,6 @@ size_t ertd_conv2d_workspace_bytes(int cin, int cout, int ks, int precision, int
 }
 
 namespace {
-// which Winograd layout ertd_conv2d dispatches (geometry only)
-void conv2d_wino_flags(int Cin, int Ca, int Cout, int ks, int mode, int act, int precision, int B, int Ho,
-                       bool* wino, bool* wino4) {
-  const bool bf = bf_prec(precision);
-  *wino4 = !bf && ks == 3 && Cout > 1 && conv_packed_floats_wino4(Cin, Cout) > 0 &&
-           ((mode == MODE_S1 && wino4_ok(Cin, Ca, Cout, Ho, B)) ||
-            (mode == MODE_UP && act == ACT_NONE && wino4s_up_ok(Cin, Ca, Cout, Ho, B)));
-  *wino = *wino4 || (!bf && ks == 3 && mode == MODE_S1 && Cout > 1 &&
-                     conv_packed_floats_wino(Cin, Cout) > 0 && conv_wino_ok(Cin, Ca, Cout, Ho));
-}
-
 // ertd_conv2d: pack (unless `pack` is false: ws already holds this shape's
 // packing from an earlier call) and launch; gnp (B, Cout, gn_np) float2: the
 // GroupNorm partials of the output from the epilogue (gn_np must be what
@@ -927,10 +918,9 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
   float* kbuf = need.kbuf_floats ? pk + a64(need.pack_floats) : nullptr;
   void* bimg = need.bimg_bytes ? (void*)(pk + a64(need.pack_floats) + a64(need.kbuf_floats)) : nullptr;
   // the Winograd path reads only its own packing: skip the direct one then
-  const int Ho_ = mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H);
   const bool bf = bf_prec(precision), split = precision == ERTD_PREC_BF16X3;
-  bool wino, wino4;
-  conv2d_wino_flags(Cin, Ca, Cout, ks, mode, act, precision, B, Ho_, &wino, &wino4);
+  const WinoRoute route = conv2d_route(Cin, Ca, Cout, ks, mode, act, precision, B, H);
+  const bool wino = route.kernel != WinoRoute::NONE, wino4 = route.pack_kind == ERTD_PACK_WINO4;
   if (gnp && (bf || gn_np < 1)) return ERTD_EINVAL;
   hipError_t e = hipSuccess;
   if (!wino && pack)
@@ -943,8 +933,7 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
   a.gn = (const float2*)gn;
   a.wpk = pk; a.bias = bias; a.ebias = ebias; a.eb_stride = eb_stride; a.res = res; a.out = out;
   a.Cin = Cin; a.Cout = Cout; a.Hs = H; a.Ws = H;
-  a.Ho = Ho_;
-  a.Wo = a.Ho;
+  a.Ho = a.Wo = conv2d_out_size(H, mode);
   if (wino) {
     float* pw = pk + a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
     if (pack && (e = wino4 ? launch_pack_conv_wino4(w, Cin, Cout, pw, s)
@@ -956,7 +945,7 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
   a.bimg = bimg;
   a.split = split ? 1 : 0;
   if (gnp) {
-    if (conv_gn_parts(ks, mode, act, a, B) != gn_np) return ERTD_EINVAL;
+    if (conv_gn_parts(ks, mode, act, a, route) != gn_np) return ERTD_EINVAL;
     a.gnp = (float2*)gnp;
   }
   e = bf ? launch_conv_bf16(ks, mode, act, a, B, s) : launch_conv(ks, mode, act, a, B, s);
@@ -985,19 +974,11 @@ int ertd_conv2d_gn_parts(int Ca, int Cb, int Cout, int ks, int mode, int act, in
   if (Ca < 1 || Cb < 0 || !conv2d_geom_ok(Cin, Cout, ks, precision, B, H, mode) || bf_prec(precision) ||
       act < ACT_NONE || act > ACT_GN)
     return 0;
-  const int Ho = mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H);
-  bool wino, wino4;
-  conv2d_wino_flags(Cin, Ca, Cout, ks, mode, act, precision, B, Ho, &wino, &wino4);
-  const Conv2dWs need = conv2d_ws(Cin, Ca, Cout, ks, precision, B, H, mode, act);
-  // the dispatch reads only which pointers are set: sentinels, as the walk's dry run
-  const float* sent = reinterpret_cast<const float*>(16);
-  ConvArgs q{};
+  ConvArgs q{};   // the geometry conv_in_ok reads
   q.Ca = Ca; q.Cb = Cb; q.Cin = Cin; q.Cout = Cout;
-  q.Hs = H; q.Ws = H; q.Ho = Ho; q.Wo = Ho;
-  q.wpk_wino4 = wino4 ? sent : nullptr;
-  q.wpk_wino = wino && !wino4 ? sent : nullptr;
-  q.ksplit_buf = wino && need.kbuf_floats ? const_cast<float*>(sent) : nullptr;
-  return conv_gn_parts(ks, mode, act, q, B);
+  q.Hs = q.Ws = H;
+  q.Ho = q.Wo = conv2d_out_size(H, mode);
+  return conv_gn_parts(ks, mode, act, q, conv2d_route(Cin, Ca, Cout, ks, mode, act, precision, B, H));
 }
 
 int ertd_conv2d_gn(const float* x, int Ca, const float* x2, int Cb, int B, int H, const float* w,
@@ -1039,15 +1020,11 @@ size_t ertd_conv_input_grad_ws_bytes(int Cin, int Cout, int B, int H, int ks, in
 }  // extern "C"
 
 namespace {
-// the gradient conv's packing: Winograd F(4x4) / F(2x2) where eligible, else direct,
-// at the head of ws (flipped, transposed)
-int input_grad_kind(int Cin, int Cout, int B, int H, int ks, int mode) {
-  const int Hg = mode == MODE_UP ? 2 * H : H;
-  if (ks == 3 && Cin > 1 && conv_packed_floats_wino4(Cout, Cin) > 0 && wino4_ok(Cout, Cout, Cin, Hg, B))
-    return ERTD_PACK_WINO4;
-  if (ks == 3 && Cin > 1 && conv_packed_floats_wino(Cout, Cin) > 0 && conv_wino_ok(Cout, Cout, Cin, Hg))
-    return ERTD_PACK_WINO;
-  return ERTD_PACK_DIRECT;
+// the gradient conv (Cin_g = Cout, Cout_g = Cin, stride 1, no activation, at the
+// resolution Hg) and with it its packing at the head of ws (flipped, transposed):
+// Winograd F(4x4) / F(2x2) where eligible, else direct
+WinoRoute input_grad_route(int Cin, int Cout, int B, int H, int ks, int mode) {
+  return conv2d_route(Cout, Cout, Cin, ks, MODE_S1, ACT_NONE, ERTD_PREC_FP32, B, mode == MODE_UP ? 2 * H : H);
 }
 
 int input_grad_impl(const float* dy, int B, int H, const float* w, int Cout, int Cin, int ks, int mode,
@@ -1072,8 +1049,8 @@ int input_grad_impl(const float* dy, int B, int H, const float* w, int Cout, int
   a.srcA = src; a.Ca = Cout; a.Cb = 0;
   a.Cin = Cout; a.Cout = Cin;
   a.Hs = a.Ws = a.Ho = a.Wo = Hg;
-  const int kind = input_grad_kind(Cin, Cout, B, H, ks, mode);
-  const bool wino4 = kind == ERTD_PACK_WINO4, wino = wino4 || kind == ERTD_PACK_WINO;
+  const WinoRoute route = input_grad_route(Cin, Cout, B, H, ks, mode);
+  const bool wino4 = route.pack_kind == ERTD_PACK_WINO4, wino = route.kernel != WinoRoute::NONE;
   hipError_t e = hipSuccess;
   if (pack)
     e = wino4 ? launch_pack_conv_wino4(w, Cout, Cin, pk, s, true)
@@ -1081,7 +1058,7 @@ int input_grad_impl(const float* dy, int B, int H, const float* w, int Cout, int
                : launch_pack_conv(w, Cout, Cin, ks, pk, s, true);
   if (e != hipSuccess) return (int)e;
   if (wino4) a.wpk_wino4 = pk; else if (wino) a.wpk_wino = pk; else a.wpk = pk;
-  if (wino && wino_ksplit_wanted(Cout, Cin, Hg, B)) {
+  if (route.ksplit == 2) {
     const size_t sc = mode == MODE_S2 ? a64((size_t)B * Cout * H * H)
                       : (mode == MODE_UP ? a64((size_t)B * Cin * 4 * H * H) : 0);
     a.ksplit_buf = scratch + sc;
@@ -1137,7 +1114,7 @@ int ertd_conv_input_grad_pack_desc(int Cin, int Cout, int B, int H, int ks, int 
                                    void* ws, ertd_pack_desc* out) {
   if (!w || !ws || !out || ertd_conv_input_grad_ws_bytes(Cin, Cout, B, H, ks, mode) == 0)
     return ERTD_EINVAL;
-  fill_desc(out, w, (float*)ws, Cout, Cin, ks, input_grad_kind(Cin, Cout, B, H, ks, mode), 1);
+  fill_desc(out, w, (float*)ws, Cout, Cin, ks, input_grad_route(Cin, Cout, B, H, ks, mode).pack_kind, 1);
   return ERTD_OK;
 }
 
@@ -1147,22 +1124,13 @@ int ertd_conv2d_pack_desc(int Cin, int Ca, int Cout, int ks, int mode, int preci
   if (!w || !ws || !out || precision != ERTD_PREC_FP32 || Ca < 1 || Ca > Cin ||
       !conv2d_geom_ok(Cin, Cout, ks, precision, B, H, mode))
     return ERTD_EINVAL;
-  const int Ho = mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H);
   float* pk = (float*)ws;
-  // (the fp32 Upsample conv has no activation: ertd_conv2d_run dispatches it with ACT_NONE)
-  const bool wino4 = ks == 3 && Cout > 1 && conv_packed_floats_wino4(Cin, Cout) > 0 &&
-                     ((mode == MODE_S1 && wino4_ok(Cin, Ca, Cout, Ho, B)) ||
-                      (mode == MODE_UP && wino4s_up_ok(Cin, Ca, Cout, Ho, B)));
-  const bool wino = wino4 || (ks == 3 && mode == MODE_S1 && Cout > 1 && conv_packed_floats_wino(Cin, Cout) > 0 &&
-                              conv_wino_ok(Cin, Ca, Cout, Ho));
-  if (wino) {
-    float* pw = pk + a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
-    fill_desc(out, w, pw, Cin, Cout, ks, wino4 ? ERTD_PACK_WINO4 : ERTD_PACK_WINO, 0);
-  } else if (ks == 3 && mode == MODE_UP) {
-    fill_desc(out, w, pk, Cin, Cout, ks, ERTD_PACK_UP, 0);
-  } else {
-    fill_desc(out, w, pk, Cin, Cout, ks, ERTD_PACK_DIRECT, 0);
-  }
+  // (the stride-1 route does not depend on the activation; the fp32 Upsample
+  // conv has none: ertd_conv2d_run dispatches it with ACT_NONE)
+  const WinoRoute route = conv2d_route(Cin, Ca, Cout, ks, mode, ACT_NONE, precision, B, H);
+  if (route.kernel != WinoRoute::NONE)   // the Winograd packings lie behind the direct one
+    pk += a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
+  fill_desc(out, w, pk, Cin, Cout, ks, route.pack_kind, 0);
   return ERTD_OK;
 }
 

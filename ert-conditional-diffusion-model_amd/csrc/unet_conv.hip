@@ -499,60 +499,32 @@ static hipError_t launch_t(const ConvArgs& a, int B, hipStream_t s) {
   return launch_w<KS, MODE, ACT, 1>(a, B, s);
 }
 
-// the fp32 Upsample conv through the F(4x4) register-weight kernel
-static bool wino4s_up_dispatchable(int ks, int mode, int act, const ConvArgs& a, int B) {
-  return ks == 3 && mode == MODE_UP && act == ACT_NONE && a.wpk_wino4 && a.Hs * 2 == a.Ho &&
-         wino4s_up_ok(a.Cin, a.Ca, a.Cout, a.Wo, B);
-}
-
-int conv_gn_parts(int ks, int mode, int act, const ConvArgs& a, int B) {
+int conv_gn_parts(int ks, int mode, int act, const ConvArgs& a, const WinoRoute& r) {
   if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN) return 0;   // conv_out
 #ifndef CONV_IN_PARTS
 #define CONV_IN_PARTS 1   // 0 (A/B only): conv_in emits no partials, the walk runs a partials pass
 #endif
   if (conv_in_ok(a, ks, mode, act)) return CONV_IN_PARTS ? a.Wo * a.Wo / 256 : 0;   // conv_in_kernel: one part per 256 px
-  if (ks == 3 && mode == MODE_S1 && wino_dispatchable(a, B)) return wino_gn_parts(a, B);
-  if (wino4s_up_dispatchable(ks, mode, act, a, B)) return (a.Wo / 4) * (a.Wo / 4) / 16;
-  return 0;
-}
-
-bool conv_gn_fold_ok(int ks, int mode, int act, const ConvArgs& a, int B) {
-  if (conv_gn_parts(ks, mode, act, a, B) == 0) return false;
-  if (ks == 3 && mode == MODE_S1 && wino_dispatchable(a, B))
-    return a.wpk_wino4 && wino4s_ok(a.Cin, a.Ca, a.Cout, a.Wo, B) && wino4s_fold_ok(a, false, B);
-  if (wino4s_up_dispatchable(ks, mode, act, a, B)) return wino4s_fold_ok(a, true, B);
-  return false;
-}
-
-bool conv_gn_consume_ok(int ks, int mode, int act, const ConvArgs& a, int B) {
-  if (ks != 3 || mode != MODE_S1 || act == ACT_NONE || a.Cout == 1 || !a.wpk_wino4) return false;
-  if (!wino_dispatchable(a, B) || !wino4s_ok(a.Cin, a.Ca, a.Cout, a.Wo, B)) return false;
-  return wino4s_gnc_ok(a, B);
-}
-
-int conv_gn_fold_target(const ConvArgs& a, int B) {
-  (void)B;
-  return wino4s_fold_target(a);
+  return r.gn_parts;
 }
 
 hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s) {
   if (a.Ho != a.Wo || a.Hs != a.Ws || a.Cin != a.Ca + a.Cb) return hipErrorInvalidValue;
-  if (a.gnp && conv_gn_parts(ks, mode, act, a, B) == 0) return hipErrorInvalidValue;
-  if (a.fold.cnt && (!a.gnp || a.fold.g.pa != a.gnp || !conv_gn_fold_ok(ks, mode, act, a, B)))
-    return hipErrorInvalidValue;
-  if (a.gnc.pa && (a.gnc.Ca + a.gnc.Cb != a.Cin || !conv_gn_consume_ok(ks, mode, act, a, B)))
-    return hipErrorInvalidValue;
   const int expect = mode == MODE_S2 ? a.Ws / 2 : (mode == MODE_UP ? a.Ws * 2 : a.Ws);
   if (a.Wo != expect) return hipErrorInvalidValue;
+  const WinoRoute r = ks == 3 ? wino_route(mode, act, a.Cin, a.Ca, a.Cout, a.Wo, B, a.wpk_wino != nullptr,
+                                           a.wpk_wino4 != nullptr, device_cu_count())
+                              : WinoRoute{};
+  if (a.gnp && conv_gn_parts(ks, mode, act, a, r) == 0) return hipErrorInvalidValue;
+  if (a.fold.cnt && (!a.gnp || a.fold.g.pa != a.gnp || !r.fold_ok)) return hipErrorInvalidValue;
+  if (a.gnc.pa && (act == ACT_NONE || !wino_gnc_ok(r, a.Cin, a.Wo, a.gnc))) return hipErrorInvalidValue;
   if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN)
     return launch_conv_out(act, a, B, PK_F32, s);
   if (conv_in_ok(a, ks, mode, act)) return launch_conv_in(a, B, PK_F32, s);
-  if (ks == 3 && mode == MODE_S1 && wino_dispatchable(a, B))
-    return launch_conv_wino(act, a, B, s);
+  if (r.kernel != WinoRoute::NONE) return launch_conv_wino(act, a, s, r);
   if (ks == 3 && mode == MODE_S1 && act == ACT_NONE) return launch_t<3, MODE_S1, ACT_NONE>(a, B, s);
   if (ks == 3 && mode == MODE_S1 && act == ACT_GN_SILU) return launch_t<3, MODE_S1, ACT_GN_SILU>(a, B, s);
   if (ks == 3 && mode == MODE_S2 && act == ACT_NONE) return launch_t<3, MODE_S2, ACT_NONE>(a, B, s);
-  if (wino4s_up_dispatchable(ks, mode, act, a, B)) return launch_conv_wino4s(act, a, B, s, device_cu_count());
   if (ks == 3 && mode == MODE_UP && act == ACT_NONE) {
     // sub-pixel: 2x2 taps per class at the source resolution (weights packed
     // by launch_pack_conv_up); the template width is the SOURCE width

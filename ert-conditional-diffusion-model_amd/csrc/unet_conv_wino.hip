@@ -552,55 +552,45 @@ int ksplit_items() {
   return v;
 }
 
-int cu_count() { return device_cu_count(); }
-
 template <int WO, int ACT, int DBG>
-hipError_t launch_wod(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_wod(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   static std::atomic<unsigned long long> attr{0};
   set_max_lds_once((const void*)conv_wino_kernel<WO, ACT, DBG>, (int)WLDS, attr);
-  const int base = (WO / 2) * (WO / 2) / 64 * (a.Cout / 64) * B;
-  // fewer tile items than the split threshold (x CUs) -> K split in two halves
-  const int nchunk = a.Cin / WKC;
-  const int ksp = (a.ksplit_buf && nchunk % 2 == 0 && nchunk >= 4 &&
-                   base < ksplit_items() * cu_count()) ? 2 : 1;
-  const int nitems = base * ksp;
-  const int grid = nitems < cu_count() ? nitems : cu_count();
-  conv_wino_kernel<WO, ACT, DBG><<<grid, WT, WLDS, s>>>(a, nitems, ksp);
+  conv_wino_kernel<WO, ACT, DBG><<<r.grid, WT, WLDS, s>>>(a, r.items, r.ksplit);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || ksp == 1) return e;
-  const size_t n = (size_t)B * a.Cout * WO * WO;
-  return launch_add_inplace(a.out, a.ksplit_buf, n, s);
+  if (e != hipSuccess || r.ksplit == 1) return e;
+  return launch_add_inplace(a.out, a.ksplit_buf, r.kbuf_floats, s);
 }
 
 template <int WO, int ACT>
-hipError_t launch_wo(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_wo(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
 #ifdef ERTD_DIAG
   if constexpr (WO == 64 && ACT == ACT_GN_SILU) {
     switch (wino_dbg()) {
-      case 1: return launch_wod<WO, ACT, 1>(a, B, s);
-      case 2: return launch_wod<WO, ACT, 2>(a, B, s);
-      case 4: return launch_wod<WO, ACT, 4>(a, B, s);
-      case 8: return launch_wod<WO, ACT, 8>(a, B, s);
-      case 7: return launch_wod<WO, ACT, 7>(a, B, s);
-      case 16: return launch_wod<WO, ACT, 16>(a, B, s);
-      case 32: return launch_wod<WO, ACT, 32>(a, B, s);
-      case 64: return launch_wod<WO, ACT, 64>(a, B, s);
-      case 23: return launch_wod<WO, ACT, 23>(a, B, s);
-      case 55: return launch_wod<WO, ACT, 55>(a, B, s);
+      case 1: return launch_wod<WO, ACT, 1>(a, s, r);
+      case 2: return launch_wod<WO, ACT, 2>(a, s, r);
+      case 4: return launch_wod<WO, ACT, 4>(a, s, r);
+      case 8: return launch_wod<WO, ACT, 8>(a, s, r);
+      case 7: return launch_wod<WO, ACT, 7>(a, s, r);
+      case 16: return launch_wod<WO, ACT, 16>(a, s, r);
+      case 32: return launch_wod<WO, ACT, 32>(a, s, r);
+      case 64: return launch_wod<WO, ACT, 64>(a, s, r);
+      case 23: return launch_wod<WO, ACT, 23>(a, s, r);
+      case 55: return launch_wod<WO, ACT, 55>(a, s, r);
       default: break;
     }
   }
 #endif
-  return launch_wod<WO, ACT, 0>(a, B, s);
+  return launch_wod<WO, ACT, 0>(a, s, r);
 }
 
 template <int ACT>
-hipError_t launch_act(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_act(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   switch (a.Wo) {
-    case 16: return launch_wo<16, ACT>(a, B, s);
-    case 32: return launch_wo<32, ACT>(a, B, s);
-    case 64: return launch_wo<64, ACT>(a, B, s);
-    case 128: return launch_wo<128, ACT>(a, B, s);
+    case 16: return launch_wo<16, ACT>(a, s, r);
+    case 32: return launch_wo<32, ACT>(a, s, r);
+    case 64: return launch_wo<64, ACT>(a, s, r);
+    case 128: return launch_wo<128, ACT>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }
@@ -624,8 +614,7 @@ hipError_t launch_add_inplace(float* out, const float* part, size_t n, hipStream
   return hipGetLastError();
 }
 
-// W = 16 takes F(4x4) only when its tile items fill the CUs without a K split
-// (U2 B=64: 128 items; split in two halves it measured no faster than F(2x2))
+// ---- the route: which kernel an fp32 3x3 conv runs on, and how ----------------------
 // ERTD_WINO4_W16=1: F(4x4) at 16x16 for every even batch (K split), A/B only
 static int wino4_w16_env() {
   static int v = [] {
@@ -645,51 +634,103 @@ static int wino4s_env() {
   return v;
 }
 
-bool wino4s_ok(int cin, int ca, int cout, int wo, int B) {
-  const int e = wino4s_env();
-  if (e == 0 || wino_env() != 1 || cin % 8 || ca % 2 || cout % 64) return false;
-  if (wo != 16 && wo != 32 && wo != 64) return false;
-  if (e == 2) return true;
-  if (e == 3) return wo != 16;
-  if (e == 4 && wo != 16) return true;
-  if (wo != 16) return false;
-  if (wino4s_items(cout, wo, B) >= cu_count()) return true;
-  // the K-split schedule (half the CUs' worth of items): only where every caller
-  // that sizes scratch (want_split: conv_wino_ok && wino_ksplit_wanted) hands the
-  // kernel its ksplit_buf -- a concatenated input with Ca % 8 != 0 runs F(2x2)
-  return wino4s_ksplit(cin, cout, wo, B) && conv_wino_ok(cin, ca, cout, wo);
+// xi split over two MFMA waves per co block (default; ERTD_WINO4S_XS=1 keeps
+// one wave with all 36 xi, A/B): U2 B=64 240.5 -> 243.0 steps/s (same box,
+// two alternations).  Needs Cin >= 16: the exchange buffer is reused across an
+// item boundary only after a barrier that every wave passes between the two uses
+int wino4s_xs() {
+  static const int v = [] {
+    return ERTD_KNOB("WINO4S_XS", 2);
+  }();
+  return v;
 }
 
-bool wino4_ok(int cin, int ca, int cout, int wo, int B) {
-  if (wino_env() != 1 || cin % 4 || ca % 4 || cout % 64) return false;
-  if (wino4s_ok(cin, ca, cout, wo, B)) return true;
-  if (wo == 16)
-    return B % 2 == 0 && (wino4_w16_env() == 1 || wino4_tile_items(cout, wo, B) >= cu_count());
-  return wo == 32 || wo == 64 || wo == 128;
+// ERTD_WINO4S_KSPLIT=0: no K split (a 16x16 layer whose items fill only half
+// the CUs then runs F(2x2), as before)
+static int wino4s_ks_env() {
+  static const int v = [] {
+    return ERTD_KNOB("WINO4S_KSPLIT", 1);
+  }();
+  return v;
 }
 
-bool wino4_ksplit(int cin, int cout, int wo, int B) {
-  if (wino4s_ok(cin, cin, cout, wo, B)) return wino4s_ksplit(cin, cout, wo, B);
-  const int nchunk = cin / 4;
-  return nchunk % 2 == 0 && nchunk >= 4 && wino4_tile_items(cout, wo, B) < ksplit_items() * cu_count();
+// ERTD_WINO4S_UP=0 keeps the sub-pixel direct kernel for the Upsample convs (A/B)
+static int wino4s_up_env() {
+  static const int v = [] {
+    return ERTD_KNOB("WINO4S_UP", 1);
+  }();
+  return v;
 }
 
-bool wino_dispatchable(const ConvArgs& a, int B) {
-  if (a.Ho != a.Wo || a.Hs != a.Ho || a.Ws != a.Wo) return false;
-  return (a.wpk_wino4 && wino4_ok(a.Cin, a.Ca, a.Cout, a.Wo, B)) ||
-         (a.wpk_wino && conv_wino_ok(a.Cin, a.Ca, a.Cout, a.Wo));
-}
+// a K split takes an even number of chunks, two or more per half
+static bool chunks_split(int nchunk) { return nchunk % 2 == 0 && nchunk >= 4; }
 
-bool wino_ksplit_wanted(int cin, int cout, int wo, int B) {
-  if (wino4_ok(cin, cin, cout, wo, B)) return wino4_ksplit(cin, cout, wo, B);
-  const int base = (wo / 2) * (wo / 2) / 64 * (cout / 64) * B;
-  const int nchunk = cin / WKC;
-  return nchunk % 2 == 0 && nchunk >= 4 && base < ksplit_items() * cu_count();
-}
+// Eligibility (Cout a multiple of 64 everywhere; ERTD_UNET_WINO=0 disables all,
+// 2 keeps F(2x2) everywhere):
+//   F4S     Cin % 8, Ca % 4, W in {32, 64}; W = 16 when its items of 64 co x 16
+//           tiles fill the CUs (U2 B=64), or fill half of them and the K splits
+//           (the B = 32 train step: 128 items for 256 CUs)
+//   F4S_UP  the Upsample conv (no activation) where F4S is (Ca even), W = the
+//           OUTPUT width; at 16x16 only where the items fill the CUs: it never splits
+//   F4      Cin, Ca % 4, W in {32, 64, 128}; W = 16 with an even batch whose tile
+//           items fill the CUs without a K split (split in two halves it
+//           measured no faster than F(2x2))
+//   F2      Cin, Ca % 8, W in {16, 32, 64, 128}
+// K split: F2 / F4 with fewer tile items than ERTD_WINO_KSPLIT x CUs (default 1),
+// F4S as above -- and only for the geometries F2 takes (Ca % 8): those are the
+// ones every caller sizes ConvArgs::ksplit_buf for.  An F2 / F4 layer outside
+// them (a concatenated input with Ca % 8 != 0) runs unsplit, F4S is not taken.
+WinoRoute wino_route(int mode, int act, int Cin, int Ca, int Cout, int Wo, int B, bool have_f2_pack,
+                     bool have_f4_pack, int cus) {
+  WinoRoute r;
+  r.pack_kind = mode == MODE_UP ? ERTD_PACK_UP : ERTD_PACK_DIRECT;
+  const bool up = mode == MODE_UP && act == ACT_NONE;
+  if ((mode != MODE_S1 && !up) || wino_env() == 0 || Cout % 64 ||
+      (Wo != 16 && Wo != 32 && Wo != 64 && Wo != 128))
+    return r;
+  const bool f2_geom = Cin % WKC == 0 && Ca % WKC == 0;
+  const bool f4 = have_f4_pack && wino_env() == 1;
+  const int ncog = Cout / 64, t4 = (Wo / 4) * (Wo / 4);   // F(4x4) tiles per sample and channel
+  int base = 0;
+  bool split = false;
 
-bool conv_wino_ok(int cin, int ca, int cout, int wo) {
-  return wino_env() != 0 && cin % WKC == 0 && ca % WKC == 0 && cout % 64 == 0 &&
-         (wo == 16 || wo == 32 || wo == 64 || wo == 128);
+  const int s_items = t4 / 16 * B * ncog, e = wino4s_env();
+  const bool s_split = wino4s_ks_env() && wino4s_xs() == 2 && Wo == 16 && Cin % 8 == 0 &&
+                       chunks_split(Cin / 8) && s_items < cus && 2 * s_items >= cus;
+  const bool s_level = e == 2 || (Wo != 16 ? (e == 3 || e == 4) : (e != 3 && (s_items >= cus || s_split)));
+  const bool f4s = f4 && e != 0 && Cin % 8 == 0 && Ca % 2 == 0 && Wo != 128 && s_level &&
+                   (!s_split || f2_geom);
+  if (up) {
+    if (!f4s || wino4s_up_env() == 0 || (Wo == 16 && s_items < cus)) return r;
+    r.kernel = WinoRoute::F4S_UP;
+    base = s_items;
+  } else if (f4s && Ca % 4 == 0) {
+    r.kernel = WinoRoute::F4S;
+    base = s_items;
+    split = s_split;
+  } else if (f4 && Cin % 4 == 0 && Ca % 4 == 0 &&
+             (Wo != 16 || (B % 2 == 0 && (wino4_w16_env() == 1 || t4 * B / 32 * ncog >= cus)))) {
+    r.kernel = WinoRoute::F4;
+    base = t4 * B / 32 * ncog;
+    split = f2_geom && chunks_split(Cin / 4) && base < ksplit_items() * cus;
+  } else if (have_f2_pack && f2_geom) {
+    r.kernel = WinoRoute::F2;
+    base = (Wo / 2) * (Wo / 2) / 64 * ncog * B;
+    split = chunks_split(Cin / WKC) && base < ksplit_items() * cus;
+  } else {
+    return r;
+  }
+  const bool f2 = r.kernel == WinoRoute::F2, s = r.kernel == WinoRoute::F4S || r.kernel == WinoRoute::F4S_UP;
+  r.ksplit = split ? 2 : 1;
+  r.kbuf_floats = split ? (size_t)B * Cout * Wo * Wo : 0;
+  r.items = base * r.ksplit;
+  r.grid = r.items < cus ? r.items : cus;
+  // (no partials from a split layer: a separate pass sums the halves after the epilogue)
+  r.gn_parts = split ? 0 : (f2 ? (Wo / 2) * (Wo / 2) / 32 : t4 / 16);
+  r.fold_ok = s && !split;   // every MFMA wave of an unsplit item arrives once
+  r.fold_target = s ? t4 / 16 * ncog : 0;
+  r.pack_kind = f2 ? ERTD_PACK_WINO : ERTD_PACK_WINO4;
+  return r;
 }
 
 size_t conv_packed_floats_wino(int cin, int cout) {
@@ -707,35 +748,19 @@ hipError_t launch_pack_conv_wino(const float* w, int cin, int cout, float* dst, 
   return hipGetLastError();
 }
 
-// parts per (sample, channel) of the GroupNorm partials the dispatched
-// Winograd kernel emits (none when it splits its K: the halves are summed by
-// a separate pass after the epilogue)
-int wino_gn_parts(const ConvArgs& a, int B) {
-  if (!wino_dispatchable(a, B)) return 0;
-  if (a.wpk_wino4 && wino4_ok(a.Cin, a.Ca, a.Cout, a.Wo, B)) {
-    if (a.ksplit_buf && wino4_ksplit(a.Cin, a.Cout, a.Wo, B)) return 0;
-    return (a.Wo / 4) * (a.Wo / 4) / 16;
+hipError_t launch_conv_wino(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
+  if (r.ksplit == 2 && !a.ksplit_buf) return hipErrorInvalidValue;
+  switch (r.kernel) {
+    case WinoRoute::F4S:
+    case WinoRoute::F4S_UP: return launch_conv_wino4s(act, a, s, r);
+    case WinoRoute::F4: return launch_conv_wino4(act, a, s, r);
+    case WinoRoute::F2: break;
+    default: return hipErrorInvalidValue;
   }
-  const int base = (a.Wo / 2) * (a.Wo / 2) / 64 * (a.Cout / 64) * B;
-  const int nchunk = a.Cin / WKC;
-  if (a.ksplit_buf && nchunk % 2 == 0 && nchunk >= 4 && base < ksplit_items() * cu_count()) return 0;
-  return (a.Wo / 2) * (a.Wo / 2) / 32;
-}
-
-hipError_t launch_conv_wino(int act, const ConvArgs& a, int B, hipStream_t s) {
-  if (a.wpk_wino4 && wino4s_ok(a.Cin, a.Ca, a.Cout, a.Wo, B) && a.Ho == a.Wo && a.Hs == a.Ho &&
-      a.Ws == a.Wo)
-    return launch_conv_wino4s(act, a, B, s, cu_count());
-  if (a.wpk_wino4 && wino4_ok(a.Cin, a.Ca, a.Cout, a.Wo, B) && a.Ho == a.Wo && a.Hs == a.Ho &&
-      a.Ws == a.Wo)
-    return launch_conv_wino4(act, a, B, s, cu_count());
-  if (!a.wpk_wino || !conv_wino_ok(a.Cin, a.Ca, a.Cout, a.Wo) || a.Ho != a.Wo || a.Hs != a.Ho ||
-      a.Ws != a.Wo)
-    return hipErrorInvalidValue;
   switch (act) {
-    case ACT_NONE: return launch_act<ACT_NONE>(a, B, s);
-    case ACT_GN_SILU: return launch_act<ACT_GN_SILU>(a, B, s);
-    case ACT_GN: return launch_act<ACT_GN>(a, B, s);
+    case ACT_NONE: return launch_act<ACT_NONE>(a, s, r);
+    case ACT_GN_SILU: return launch_act<ACT_GN_SILU>(a, s, r);
+    case ACT_GN: return launch_act<ACT_GN>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }

@@ -656,18 +656,13 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, int cin, int cout
 }
 
 template <int WO, int ACT, int DBG>
-hipError_t launch_wo4d(const ConvArgs& a, int B, hipStream_t s, int cus) {
+hipError_t launch_wo4d(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   static std::atomic<unsigned long long> attr{0};
   set_max_lds_once((const void*)conv_wino4_kernel<WO, ACT, DBG>, (int)WLDS_LAUNCH, attr);
-  const int base = wino4_tile_items(a.Cout, a.Wo, B);
-  const int ksp = wino4_ksplit(a.Cin, a.Cout, a.Wo, B) && a.ksplit_buf ? 2 : 1;
-  const int nitems = base * ksp;
-  const int grid = nitems < cus ? nitems : cus;
-  conv_wino4_kernel<WO, ACT, DBG><<<grid, WT, WLDS_LAUNCH, s>>>(a, nitems, ksp);
+  conv_wino4_kernel<WO, ACT, DBG><<<r.grid, WT, WLDS_LAUNCH, s>>>(a, r.items, r.ksplit);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || ksp == 1) return e;
-  const size_t n = (size_t)B * a.Cout * WO * WO;
-  return launch_add_inplace(a.out, a.ksplit_buf, n, s);
+  if (e != hipSuccess || r.ksplit == 1) return e;
+  return launch_add_inplace(a.out, a.ksplit_buf, r.kbuf_floats, s);
 }
 
 #ifdef ERTD_DIAG
@@ -682,33 +677,33 @@ int wino4_dbg() {
 #endif
 
 template <int WO, int ACT>
-hipError_t launch_wo4(const ConvArgs& a, int B, hipStream_t s, int cus) {
+hipError_t launch_wo4(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
 #ifdef ERTD_DIAG
   if constexpr (WO == 64 && ACT == ACT_GN_SILU) {
     switch (wino4_dbg()) {
-      case 1: return launch_wo4d<WO, ACT, 1>(a, B, s, cus);
-      case 2: return launch_wo4d<WO, ACT, 2>(a, B, s, cus);
-      case 3: return launch_wo4d<WO, ACT, 3>(a, B, s, cus);
-      case 4: return launch_wo4d<WO, ACT, 4>(a, B, s, cus);
-      case 8: return launch_wo4d<WO, ACT, 8>(a, B, s, cus);
-      case 16: return launch_wo4d<WO, ACT, 16>(a, B, s, cus);
-      case 32: return launch_wo4d<WO, ACT, 32>(a, B, s, cus);
-      case 7: return launch_wo4d<WO, ACT, 7>(a, B, s, cus);
-      case 23: return launch_wo4d<WO, ACT, 23>(a, B, s, cus);
+      case 1: return launch_wo4d<WO, ACT, 1>(a, s, r);
+      case 2: return launch_wo4d<WO, ACT, 2>(a, s, r);
+      case 3: return launch_wo4d<WO, ACT, 3>(a, s, r);
+      case 4: return launch_wo4d<WO, ACT, 4>(a, s, r);
+      case 8: return launch_wo4d<WO, ACT, 8>(a, s, r);
+      case 16: return launch_wo4d<WO, ACT, 16>(a, s, r);
+      case 32: return launch_wo4d<WO, ACT, 32>(a, s, r);
+      case 7: return launch_wo4d<WO, ACT, 7>(a, s, r);
+      case 23: return launch_wo4d<WO, ACT, 23>(a, s, r);
       default: break;
     }
   }
 #endif
-  return launch_wo4d<WO, ACT, 0>(a, B, s, cus);
+  return launch_wo4d<WO, ACT, 0>(a, s, r);
 }
 
 template <int ACT>
-hipError_t launch_act4(const ConvArgs& a, int B, hipStream_t s, int cus) {
+hipError_t launch_act4(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   switch (a.Wo) {
-    case 16: return launch_wo4<16, ACT>(a, B, s, cus);
-    case 32: return launch_wo4<32, ACT>(a, B, s, cus);
-    case 64: return launch_wo4<64, ACT>(a, B, s, cus);
-    case 128: return launch_wo4<128, ACT>(a, B, s, cus);
+    case 16: return launch_wo4<16, ACT>(a, s, r);
+    case 32: return launch_wo4<32, ACT>(a, s, r);
+    case 64: return launch_wo4<64, ACT>(a, s, r);
+    case 128: return launch_wo4<128, ACT>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }
@@ -722,8 +717,6 @@ extern "C" int ertd_diag_wino4_stamps(unsigned* host, size_t n) {
                                   hipMemcpyDeviceToHost);
 }
 #endif
-
-int wino4_tile_items(int cout, int wo, int B) { return (wo / 4) * (wo / 4) * B / 32 * (cout / 64); }
 
 size_t conv_packed_floats_wino4(int cin, int cout) {
   if (cin % WKC || cout % 64) return 0;
@@ -739,11 +732,11 @@ hipError_t launch_pack_conv_wino4(const float* w, int cin, int cout, float* dst,
   return hipGetLastError();
 }
 
-hipError_t launch_conv_wino4(int act, const ConvArgs& a, int B, hipStream_t s, int cus) {
+hipError_t launch_conv_wino4(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   switch (act) {
-    case ACT_NONE: return launch_act4<ACT_NONE>(a, B, s, cus);
-    case ACT_GN_SILU: return launch_act4<ACT_GN_SILU>(a, B, s, cus);
-    case ACT_GN: return launch_act4<ACT_GN>(a, B, s, cus);
+    case ACT_NONE: return launch_act4<ACT_NONE>(a, s, r);
+    case ACT_GN_SILU: return launch_act4<ACT_GN_SILU>(a, s, r);
+    case ACT_GN: return launch_act4<ACT_GN>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }

@@ -25,7 +25,7 @@
 // output transform, bias / emb / residual epilogue and the GroupNorm partials
 // (one part per 16 tiles, as conv_wino4_kernel) are per MFMA wave.
 // K split (ksp = 2, XS = 2 only, never for the Upsample convs): where the items
-// fill half the CUs or more but not all (wino4s_ksplit: the 16x16 level of the
+// fill half the CUs or more but not all (wino_route: the 16x16 level of the
 // B = 32 train step), an item is (K half, co group, block) with the two halves
 // of a (co group, block) adjacent; half 0 sweeps channels [0, Cin/2) and writes
 // out with bias / emb / residual, half 1 sweeps [Cin/2, Cin) and writes its raw
@@ -210,7 +210,7 @@ __device__ __forceinline__ int itm_half(const ItemWalk& w, int il) { return w.at
 // instantiation (FOLD = false) has none of it: no static LDS word in front of
 // the dynamic V buffers, no per-item branches.
 // GNC: the input's GroupNorm finalize runs in this kernel's prologue
-// (ConvArgs::gnc, conv_gn_consume_ok): before the first chunk the 8 MFMA waves
+// (ConvArgs::gnc, wino_gnc_ok): before the first chunk the 8 MFMA waves
 // -- idle until the producers stage chunk 0 -- merge the partials of every
 // item's sample into an LDS table of {scale, shift} per (item, channel)
 // (gn_group_finalize_regs: the arithmetic of gn_finalize_kernel, so the same
@@ -770,7 +770,7 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
   }
   if constexpr (GNC) {
     // job j = item il, groups 4 jg .. 4 jg + 3 (ng4 = ceil(G / 4) jobs per item):
-    // wave w of the 8 takes jobs w, w + 8, ... (conv_gn_consume_ok: <= 4 each)
+    // wave w of the 8 takes jobs w, w + 8, ... (wino_gnc_ok: <= 4 each)
     constexpr int JM = GNC_JM;
     const int ng4 = (a.gnc.groups + 3) / 4;
     int smp[JM], jg[JM], row[JM];
@@ -999,17 +999,6 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 
 }
 
-// xi split over two MFMA waves per co block (default; ERTD_WINO4S_XS=1 keeps
-// one wave with all 36 xi, A/B): U2 B=64 240.5 -> 243.0 steps/s (same box,
-// two alternations).  Needs Cin >= 16: the exchange buffer is reused across an
-// item boundary only after a barrier that every wave passes between the two uses
-static int wino4s_xs() {
-  static const int v = [] {
-    return ERTD_KNOB("WINO4S_XS", 2);
-  }();
-  return v;
-}
-
 }  // namespace
 
 #ifdef WINO4S_STAMP
@@ -1023,25 +1012,6 @@ extern "C" int ertd_diag_wino4s_stamps_clear() {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_w4s_stamps), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
 }
 #endif
-
-// ERTD_WINO4S_KSPLIT=0: no K split (a 16x16 layer whose items fill only half
-// the CUs then runs F(2x2), as before)
-static int wino4s_ks_env() {
-  static const int v = [] {
-    return ERTD_KNOB("WINO4S_KSPLIT", 1);
-  }();
-  return v;
-}
-
-// the xi-split kernel splits its K in two halves when its items fill half the
-// CUs or more but not all of them (the 16x16 level of the B = 32 train step:
-// 128 items of 64 co x 16 tiles for 256 CUs), given an even chunk count >= 4
-bool wino4s_ksplit(int cin, int cout, int wo, int B) {
-  if (!wino4s_ks_env() || wino4s_xs() != 2 || wo != 16 || cin % CCH || cout % 64) return false;
-  const int nchunk = cin / CCH;
-  const int items = wino4s_items(cout, wo, B), cus = device_cu_count();
-  return nchunk % 2 == 0 && nchunk >= 4 && items < cus && 2 * items >= cus;
-}
 
 // contiguous walk (items bid * cw ...), diagnostic builds only:
 // ERTD_WINO4S_CWALK=1 takes it for every xi-split layer that can.  Measured
@@ -1058,29 +1028,28 @@ static int wino4s_cwalk_env() {
 // items per workgroup of the contiguous walk, or 0 where it does not apply:
 // the xi-split kernel (Cin >= 16) without a K split, items an exact multiple of
 // the grid, each workgroup's run inside one sample
-static int wino4s_cw_geom(const ConvArgs& a, int wo, int B, int ksp, int cus) {
-  if (ksp != 1 || wino4s_xs() != 2 || a.Cin < 16 || a.Cout % 64) return 0;
-  const int nitems = wino4s_items(a.Cout, wo, B);
-  const int grid = nitems < cus ? nitems : cus;
-  if (grid < 1 || nitems % grid) return 0;
-  const int cw = nitems / grid;
-  const int per_sample = (wo / 4) * (wo / 4) / 16 * (a.Cout / 64);
-  return per_sample % cw == 0 ? cw : 0;
+static int wino4s_cw_geom(int Cin, const WinoRoute& r) {
+  if (r.ksplit != 1 || wino4s_xs() != 2 || Cin < 16 || r.grid < 1 || r.items % r.grid) return 0;
+  const int cw = r.items / r.grid;
+  return r.fold_target % cw == 0 ? cw : 0;   // (fold_target: the items of one sample)
 }
 
 namespace {
 
-int wino4s_cwalk(const ConvArgs& a, int wo, int B, int ksp, int cus) {
+int wino4s_cwalk(const ConvArgs& a, const WinoRoute& r) {
   if (wino4s_cwalk_env() == 0 || a.fold.cnt) return 0;
-  return wino4s_cw_geom(a, wo, B, ksp, cus);
+  return wino4s_cw_geom(a.Cin, r);
 }
 
 template <int WO, int ACT, bool UP, int XS>
-hipError_t launch_wo4x(const ConvArgs& a, int B, hipStream_t s, int cus, int ksp) {
+hipError_t launch_wo4x(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   constexpr size_t lds = WLDS + (XS == 2 ? (size_t)4 * 2 * 8 * 256 * sizeof(float) : 0);
-  const int nitems = wino4s_items(a.Cout, WO, B) * ksp;
-  const int grid = nitems < cus ? nitems : cus;
-  const int cw = wino4s_cwalk(a, WO, B, ksp, cus);
+  const int nitems = r.items, grid = r.grid, ksp = r.ksplit;
+  // the fold and the consumer-side finalize ride on unsplit items only (the
+  // latter's branch below returns before the pass that sums a split's halves);
+  // the single-wave variant has no split either
+  if (ksp != 1 && (a.gnc.pa || a.fold.cnt || XS != 2)) return hipErrorInvalidValue;
+  const int cw = wino4s_cwalk(a, r);
 #ifdef ERTD_DIAG
   if (a.fold.cnt) {
     static std::atomic<unsigned long long> attr{0};
@@ -1109,47 +1078,26 @@ hipError_t launch_wo4x(const ConvArgs& a, int B, hipStream_t s, int cus, int ksp
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || ksp == 1) return e;
-  return launch_add_inplace(a.out, a.ksplit_buf, (size_t)B * a.Cout * WO * WO, s);
+  return launch_add_inplace(a.out, a.ksplit_buf, r.kbuf_floats, s);
 }
 
 template <int WO, int ACT, bool UP>
-hipError_t launch_wo4s(const ConvArgs& a, int B, hipStream_t s, int cus) {
-  if (wino4s_xs() == 2 && a.Cin >= 16) {
-    // the split geometry (wino4s_ok's second case) always comes with its buffer:
-    // without one the kernel would run unsplit on half the CUs -- refuse instead
-    const bool spl = !UP && wino4s_ksplit(a.Cin, a.Cout, WO, B) && wino4s_items(a.Cout, WO, B) < cus;
-    if (spl && !a.ksplit_buf) return hipErrorInvalidValue;
-    const int ksp = spl ? 2 : 1;
-    return launch_wo4x<WO, ACT, UP, 2>(a, B, s, cus, ksp);
-  }
-  return launch_wo4x<WO, ACT, UP, 1>(a, B, s, cus, 1);
+hipError_t launch_wo4s(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
+  if (wino4s_xs() == 2 && a.Cin >= 16) return launch_wo4x<WO, ACT, UP, 2>(a, s, r);
+  return launch_wo4x<WO, ACT, UP, 1>(a, s, r);
 }
 
-template <int ACT>
-hipError_t launch_act4s(const ConvArgs& a, int B, hipStream_t s, int cus) {
+template <int ACT, bool UP>
+hipError_t launch_act4s(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   switch (a.Wo) {
-    case 16: return launch_wo4s<16, ACT, false>(a, B, s, cus);
-    case 32: return launch_wo4s<32, ACT, false>(a, B, s, cus);
-    case 64: return launch_wo4s<64, ACT, false>(a, B, s, cus);
+    case 16: return launch_wo4s<16, ACT, UP>(a, s, r);
+    case 32: return launch_wo4s<32, ACT, UP>(a, s, r);
+    case 64: return launch_wo4s<64, ACT, UP>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }
 
 }  // namespace
-
-int wino4s_items(int cout, int wo, int B) { return (wo / 4) * (wo / 4) / 16 * B * (cout / 64); }
-
-// the GroupNorm fold (ConvArgs::fold) rides on the emitted partials: items
-// without a K split; every MFMA wave of an item arrives once
-bool wino4s_fold_ok(const ConvArgs& a, bool up, int B) {
-  if (a.Cin % CCH || a.Ca % 2 || a.Cout % 64) return false;
-  (void)B;
-  const int xs = wino4s_xs() == 2 && a.Cin >= 16 ? 2 : 1;
-  if (xs == 2 && !up && wino4s_ksplit(a.Cin, a.Cout, a.Wo, B) && wino4s_items(a.Cout, a.Wo, B) < device_cu_count())
-    return false;
-  return true;
-}
-int wino4s_fold_target(const ConvArgs& a) { return (a.Wo / 4) * (a.Wo / 4) / 16 * (a.Cout / 64); }
 
 // the consumer-side GroupNorm finalize (ConvArgs::gnc): a GN+act layer of the
 // xi-split kernel without a K split (stride-1 only: the Upsample convs take no
@@ -1159,58 +1107,33 @@ int wino4s_fold_target(const ConvArgs& a) { return (a.Wo / 4) * (a.Wo / 4) / 16 
 // 64x64 layers, U2 B=64), more than the 3.3 us launch it replaces.  Same box,
 // U2 B=64, three alternations: 250.1 steps/s without (ERTD_UNET_GNC=0), 251.9
 // on every eligible layer (1), 252.1 at <= 2 items (3, the default; 2: one item)
-bool wino4s_gnc_ok(const ConvArgs& a, int B) {
+bool wino_gnc_ok(const WinoRoute& r, int Cin, int Wo, const GnPartArgs& g) {
   static const int env = [] {
     return ERTD_KNOB("UNET_GNC", 3);
   }();
-  const GnPartArgs& g = a.gnc;
-  if (!env || wino4s_xs() != 2 || a.Cin < 16 || a.Cin % CCH || a.Ca % 2 || a.Cout % 64) return false;
-  if (a.Wo != 16 && a.Wo != 32 && a.Wo != 64) return false;
-  if (!g.pa || g.groups < 1 || g.Ca + g.Cb != a.Cin || a.Cin % g.groups || g.npa < 1 ||
-      (g.Cb > 0 && (!g.pb || g.npb < 1)) || g.HW != a.Wo * a.Wo || g.HW % g.npa ||
+  if (r.kernel != WinoRoute::F4S || r.ksplit != 1) return false;
+  if (!env || wino4s_xs() != 2 || Cin < 16) return false;
+  if (!g.pa || g.groups < 1 || g.Ca + g.Cb != Cin || Cin % g.groups || g.npa < 1 ||
+      (g.Cb > 0 && (!g.pb || g.npb < 1)) || g.HW != Wo * Wo || g.HW % g.npa ||
       (g.Cb > 0 && g.HW % g.npb))
     return false;
-  const int cus = device_cu_count();
-  const bool spl = wino4s_ksplit(a.Cin, a.Cout, a.Wo, B) && wino4s_items(a.Cout, a.Wo, B) < cus;
-  if (spl) return false;
-  const int nitems = wino4s_items(a.Cout, a.Wo, B);
-  const int grid = nitems < cus ? nitems : cus;
-  const int nloc = wino4s_cwalk_env() ? wino4s_cw_geom(a, a.Wo, B, 1, cus) : (nitems + grid - 1) / grid;
-  const int cpg = a.Cin / g.groups;
+  const int nloc = wino4s_cwalk_env() ? wino4s_cw_geom(Cin, r) : (r.items + r.grid - 1) / r.grid;
+  const int cpg = Cin / g.groups;
   const int np = g.npa > g.npb ? g.npa : g.npb;
   if (env == 2 && nloc > 1) return false;   // (diagnostic: single-item workgroups only)
   if (env == 3 && nloc > 2) return false;   // (diagnostic: at most two items per workgroup)
   return nloc > 0 && nloc * ((g.groups + 3) / 4) <= 8 * GNC_JM && cpg <= GN_LPG &&
-         cpg * np <= GN_LPG * GNC_KM && nloc * a.Cin <= GNC_TAB;
+         cpg * np <= GN_LPG * GNC_KM && nloc * Cin <= GNC_TAB;
 }
 
-// ERTD_WINO4S_UP=0 keeps the sub-pixel direct kernel for the Upsample convs (A/B)
-bool wino4s_up_ok(int cin, int ca, int cout, int wo, int B) {
-  static const int env = [] {
-    return ERTD_KNOB("WINO4S_UP", 1);
-  }();
-  // (at 16x16 only where the items fill the CUs: the Upsample conv has no K split)
-  return env != 0 && wino4s_ok(cin, ca, cout, wo, B) && (wo == 16 || wo == 32 || wo == 64) &&
-         (wo != 16 || wino4s_items(cout, wo, B) >= device_cu_count());
-}
-
-hipError_t launch_conv_wino4s(int act, const ConvArgs& a, int B, hipStream_t s, int cus) {
-  if (a.Cin % CCH || a.Ca % 2 || a.Cout % 64 || !a.wpk_wino4 || a.Ho != a.Wo || a.Hs != a.Ws)
-    return hipErrorInvalidValue;
-  if (a.Hs * 2 == a.Wo) {   // Upsample conv (no activation)
-    if (act != ACT_NONE) return hipErrorInvalidValue;
-    switch (a.Wo) {
-      case 16: return launch_wo4s<16, ACT_NONE, true>(a, B, s, cus);
-      case 32: return launch_wo4s<32, ACT_NONE, true>(a, B, s, cus);
-      case 64: return launch_wo4s<64, ACT_NONE, true>(a, B, s, cus);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (a.Hs != a.Wo) return hipErrorInvalidValue;
+hipError_t launch_conv_wino4s(int act, const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
+  if (r.kernel == WinoRoute::F4S_UP)   // Upsample conv (no activation)
+    return act == ACT_NONE ? launch_act4s<ACT_NONE, true>(a, s, r) : hipErrorInvalidValue;
+  if (r.kernel != WinoRoute::F4S) return hipErrorInvalidValue;
   switch (act) {
-    case ACT_NONE: return launch_act4s<ACT_NONE>(a, B, s, cus);
-    case ACT_GN_SILU: return launch_act4s<ACT_GN_SILU>(a, B, s, cus);
-    case ACT_GN: return launch_act4s<ACT_GN>(a, B, s, cus);
+    case ACT_NONE: return launch_act4s<ACT_NONE, false>(a, s, r);
+    case ACT_GN_SILU: return launch_act4s<ACT_GN_SILU, false>(a, s, r);
+    case ACT_GN: return launch_act4s<ACT_GN, false>(a, s, r);
     default: return hipErrorInvalidValue;
   }
 }

@@ -62,6 +62,10 @@ CASES = [  # (Ca, Cb, Cout, H, ks, mode, act)
     (32, 32, 64, 32, 3, "same", "none"),         # no activation, concatenated input
     (256, 0, 128, 16, 3, "same", "gn"),          # GroupNorm without SiLU
     (384, 128, 256, 16, 3, "same", "gn_silu"),   # U2's widest concat (K = 512)
+    # the unsplit F(2x2) and LDS-weight F(4x4) launches (at B = 2 every larger layer splits its K)
+    (16, 8, 64, 16, 3, "same", "gn_silu"),       # F(2x2): 3 chunks of 8 do not split
+    (12, 0, 64, 32, 3, "same", "gn_silu"),       # F(4x4): Cin % 8 != 0, 3 chunks of 4
+    (12, 52, 64, 128, 3, "same", "gn_silu"),     # F(4x4): Ca % 8 != 0 -- no split buffer, runs unsplit
     # ... and shapes it does not take (direct implicit GEMM)
     (20, 0, 64, 32, 3, "same", "gn_silu"),       # Cin % 8 != 0
     (64, 0, 96, 32, 3, "same", "gn_silu"),       # Cout % 64 != 0

@@ -261,6 +261,24 @@ def test_conv2d_workspace_covers_launch_scratch():
     assert lib.ertd_mse_loss(None, None, 4, None, None, None, 0, None) == _lib.ERTD_EINVAL
 
 
+def test_conv_dispatch_matches_fixture():
+    """The conv dispatch as the host queries show it (kernel family, K split,
+    GroupNorm partial count, workspace, weight packing; whole-walk workspace and
+    packed size) equals tests/golden/dispatch_kat.npz row for row
+    (make_dispatch_golden.py: the grids and the queries)."""
+    from conftest import load_golden
+    from make_dispatch_golden import dispatch_tables
+    kat = load_golden("dispatch_kat.npz")
+    got = dispatch_tables()
+    assert sorted(kat.files) == sorted(got)
+    for name, tab in got.items():
+        want = kat[name]
+        assert tab.shape == want.shape, name
+        bad = np.flatnonzero((tab != want).reshape(len(tab), -1).any(axis=1))
+        assert bad.size == 0, f"{name}: {bad.size} rows differ, first {bad[:5].tolist()}: " \
+                              f"{tab[bad[0]].tolist()} != {want[bad[0]].tolist()}"
+
+
 def test_bf16_unet_under_autograd_raises():
     """A bf16-operand U-Net has no backward: forward under autograd raises a
     RuntimeError that says so (before any device work) instead of returning
