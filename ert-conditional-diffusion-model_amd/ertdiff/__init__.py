@@ -20,8 +20,9 @@ from .unet_train import UNetTrainPlan, unet_train_backward, unet_train_forward, 
 from .kde import ensemble_mode, kde_mode, mode_kde_calculation
 from .stats import (WSSE_metric, accuracy_score, avg_prop_indicator_function, coverage_counts,
                     coverage_curve, coverage_from_counts, ensemble_moments, ensemble_percentile,
-                    ensemble_summary, goodness_score, interval_fractions,
-                    parameter_uncertainty_metrics, preccision_score, uncertainty_metrics, wsse)
+                    ensemble_summary, goodness_score, interval_fractions, mse,
+                    parameter_uncertainty_metrics, preccision_score, sort_rows, uncertainty_metrics,
+                    wasserstein, wasserstein_distance, wsse)
 
 __all__ = [
     "ConditionalDiffusionModel", "get_timestep_embedding", "get_diffusion_schedule", "q_sample",
@@ -35,5 +36,5 @@ __all__ = [
     "ensemble_percentile", "ensemble_moments", "ensemble_summary", "coverage_curve", "coverage_counts",
     "coverage_from_counts", "interval_fractions", "parameter_uncertainty_metrics", "wsse", "WSSE_metric",
     "avg_prop_indicator_function", "accuracy_score", "preccision_score", "goodness_score",
-    "uncertainty_metrics",
+    "uncertainty_metrics", "sort_rows", "wasserstein", "wasserstein_distance", "mse",
 ]

@@ -181,6 +181,11 @@ SIGNATURES = {
     "ertd_ens_moments": (_I, [_VP, _I, _I, _LL, _LL, _VP, _I, _VP, _VP, _VP]),
     "ertd_coverage": (_I, [_VP, _VP, _I, _I, _LL, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
     "ertd_wsse": (_I, [_VP, _VP, _I, _I, _LL, _I, ctypes.c_double, ctypes.c_double, _VP, _VP]),
+    "ertd_rows_sort_tile": (_I, [_I]),
+    "ertd_rows_sort_ws_bytes": (_SZ, [_I, _I, _LL]),
+    "ertd_rows_sort": (_I, [_VP, _I, _I, _LL, _LL, _VP, _VP, _SZ, _VP]),
+    "ertd_wasserstein_ws_bytes": (_SZ, [_I, _I, _LL, _LL]),
+    "ertd_wasserstein": (_I, [_VP, _I, _I, _LL, _LL, _VP, _LL, _VP, _VP, _SZ, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

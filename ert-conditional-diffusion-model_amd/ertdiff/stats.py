@@ -9,7 +9,11 @@ per-cell statistics of the simulated ensemble (:867-876) and the WSSE of every
 realisation and survey (:767-787).  Here the order statistics, the indicator
 counts, the moments and the WSSE come from float64 kernels (csrc/ensstats.hip)
 that read the arrays where they are; percentiles and coverage carry numpy's
-bits.  Only the three scores of a 30-point curve are host numpy.
+bits.  Only the three scores of a 30-point curve are host numpy.  The
+Wasserstein-1 distance of each simulated image to the observation (:860,
+:898-899, scipy.stats.wasserstein_distance) and the sort of long rows behind
+it come from csrc/rowsort.hip; the per-realisation MSE (:927-949) is a WSSE
+with unit weights.
 
     ensemble_percentile(x, percents, valid=None)    -> (len(percents), *cells) float64
     ensemble_summary(sim_data, percentiles=(25, 50, 75)) -> dict mean/std/var/percentiles/cv
@@ -17,6 +21,10 @@ bits.  Only the three scores of a 30-point curve are host numpy.
                                  -> avg_proportion (K,), per parameter (P, K), counts, cols
     parameter_uncertainty_metrics(generated, true)  -> (P, 3) accuracy, precision, goodness
     wsse(sim_data, observations, A=0.1, B=0.01)     -> (n, E) float64
+    mse(sim_data, observations)                     -> (n,) float64
+    sort_rows(x)                                    -> x's shape and dtype, rows ascending
+    wasserstein(sim_data, observations)             -> (n,) float64
+    wasserstein_distance(u_values, v_values)        -> float (scipy's name and signature)
     avg_prop_indicator_function, accuracy_score, preccision_score, goodness_score,
     uncertainty_metrics, WSSE_metric                 (the reference's names and spellings)
 """
@@ -323,3 +331,109 @@ def WSSE_metric(A, B, predictions, observations, device=None):
     o64, p64 = o.reshape(-1).to(torch.float64), p.reshape(-1).to(torch.float64)
     sd = A * o64.abs() + B
     return float(value.item()), (p64 - o64) ** 2 / sd ** 2
+
+
+def mse(sim_data, observations, device=None) -> torch.Tensor:
+    """sklearn's mean_squared_error of every flattened realisation against the
+    flattened observation (:927-930, :940-941): sim_data (n, *cells),
+    observations of the same number of values, same dtype; (n,) float64 on the
+    device.  It is the WSSE with the weight (0 |o| + 1)^2, exactly 1."""
+    n = int(sim_data.shape[0]) if len(sim_data.shape) else 0
+    if n < 1 or int(np.prod(sim_data.shape)) == 0:
+        raise ValueError("ertdiff: sim_data is empty")
+    return wsse(sim_data.reshape(n, -1, 1), observations.reshape(-1, 1), A=0.0, B=1.0,
+                device=device)[:, 0]
+
+
+# ---- row sort and Wasserstein-1 distance (csrc/rowsort.hip) ---------------------
+
+MAX_ROW = 1 << 24                  # keys per row
+
+
+def _row_view(t: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """(tensor, M, ld) of n rows of M values: a 2-D view whose rows are
+    contiguous is read in place through its row pitch (as _rows does for
+    columns); anything else is flattened per row into a contiguous copy."""
+    n = t.shape[0]
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t, int(t.shape[1]), int(t.stride(0))
+    t = t.reshape(n, -1).contiguous()
+    return t, int(t.shape[1]), int(t.shape[1])
+
+
+def _check_rows(n: int, M: int, name: str) -> None:
+    if n < 1 or M < 1:
+        raise ValueError(f"ertdiff: {name} is empty")
+    if M > MAX_ROW:
+        raise ValueError(f"ertdiff: {name} holds {M} values per row, more than {MAX_ROW}")
+
+
+def sort_rows(x, device=None) -> torch.Tensor:
+    """np.sort(x, axis=-1) of x (n, M) or (M,), float32 or float64, on the
+    device: every row ascending, NaNs last, bit for bit.  Returns a sorted copy
+    in the input's shape and dtype.  Rows of any length up to 2^24 (many
+    workgroups sort one row); a 2-D view with contiguous rows is read in place."""
+    t = _as_tensor(x, device, "x")
+    if t.dim() not in (1, 2):
+        raise ValueError(f"ertdiff: x must be (n, M) or (M,), got {tuple(t.shape)}")
+    shape = tuple(t.shape)
+    t2 = t.unsqueeze(0) if t.dim() == 1 else t
+    _check_rows(t2.shape[0], t2.shape[1], "x")
+    dev = _lib.require_device(t2)
+    t2, M, ld = _row_view(t2)
+    n, dt = t2.shape[0], _DTYPES[t2.dtype]
+    out = torch.empty((n, M), dtype=t2.dtype, device=dev)
+    with torch.cuda.device(dev):
+        lib = _lib.lib()
+        need = lib.ertd_rows_sort_ws_bytes(dt, n, M)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        _lib.check(lib.ertd_rows_sort(t2.data_ptr(), dt, n, M, ld, out.data_ptr(), _lib.ptr(ws), need,
+                                      _lib.stream_of(dev)), "rows_sort")
+    return out.reshape(shape)
+
+
+def wasserstein(sim_data, observations, device=None) -> torch.Tensor:
+    """scipy.stats.wasserstein_distance(sim_data[s].flatten(),
+    observations.flatten()) for every realisation s (:860, :898-899).
+
+    sim_data (n, *cells) and observations of any shape, same dtype (float32 or
+    float64), device tensors or numpy arrays; the two sides may hold different
+    numbers of values.  Returns (n,) float64 on the device: scipy's terms bit
+    for bit, added in a fixed order.  A NaN in a realisation makes its
+    distance NaN, a NaN in the observation every distance."""
+    u = _as_tensor(sim_data, device, "sim_data")
+    if u.dim() < 2:
+        raise ValueError(f"ertdiff: sim_data must be (n, *cells), got {tuple(u.shape)}")
+    v = _as_tensor(observations, u.device if isinstance(observations, np.ndarray) else None,
+                   "observations")
+    if v.dtype != u.dtype:
+        raise ValueError(f"ertdiff: sim_data ({u.dtype}) and observations ({v.dtype}) must share a dtype")
+    _check_rows(u.shape[0], int(np.prod(u.shape[1:])), "sim_data")
+    _check_rows(1, v.numel(), "observations")
+    dev = _lib.require_device(u, v)
+    u, Mu, ld = _row_view(u)
+    v = v.reshape(-1).contiguous()
+    n, Mv, dt = u.shape[0], v.numel(), _DTYPES[u.dtype]
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        lib = _lib.lib()
+        need = lib.ertd_wasserstein_ws_bytes(dt, n, Mu, Mv)
+        if not need:
+            raise ValueError(f"ertdiff: wasserstein cannot take {n} rows of {Mu} against {Mv} values")
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(lib.ertd_wasserstein(u.data_ptr(), dt, n, Mu, ld, v.data_ptr(), Mv, out.data_ptr(),
+                                        ws.data_ptr(), need, _lib.stream_of(dev)), "wasserstein")
+    return out
+
+
+def wasserstein_distance(u_values, v_values, u_weights=None, v_weights=None) -> float:
+    """The reference's import (:13), scipy's name and signature, for two
+    one-dimensional samples.  Weighted distributions are not on the device."""
+    if u_weights is not None or v_weights is not None:
+        raise ValueError("ertdiff: weighted distributions are not on the device; "
+                         "wasserstein_distance takes u_weights = v_weights = None")
+    if not isinstance(u_values, (np.ndarray, torch.Tensor)):
+        u_values = np.asarray(u_values, dtype=np.float64)
+    if not isinstance(v_values, (np.ndarray, torch.Tensor)):
+        v_values = np.asarray(v_values, dtype=np.float64)
+    return float(wasserstein(u_values.reshape(1, -1), v_values.reshape(-1))[0].item())

@@ -684,6 +684,41 @@ int ertd_coverage(const void* ens, const void* truth, int dtype, int S, long lon
 int ertd_wsse(const void* pred, const void* obs, int dtype, int n, long long M, int E, double A,
               double B, double* out, void* stream);
 
+/* ---- Row sort and Wasserstein-1 distance (csrc/rowsort.hip) -------------------
+ * Replaces the host scipy.stats.wasserstein_distance the reference calls on
+ * a flattened simulated ERT image and the flattened conditional observation:
+ * ERT_Conditional_Diffusion.py:860 (each of the best simulations) and
+ * :898-899 (the ensemble mean and mode), 65,702 values per side.  Rows are
+ * contiguous, row s at x + s * ld (ld >= M), float32 or float64 (dtype); a
+ * row is sorted by many workgroups: LDS tile sorts, then merge passes in
+ * global memory between `out` and the caller's workspace.  Deterministic; no
+ * allocation, no host synchronisation.  Both calls require n >= 1,
+ * 1 <= M <= 2^24 and n * ceil(M / 1024) <= 2^22, and return ERTD_EINVAL
+ * otherwise, ERTD_ENOSPC for a workspace shorter than the _ws_bytes call
+ * reports (0 for arguments the call would reject).                          */
+/* keys per LDS tile for this dtype (tests build their edge shapes from it);
+ * 0 for an unknown dtype                                                    */
+int ertd_rows_sort_tile(int dtype);
+size_t ertd_rows_sort_ws_bytes(int dtype, int n, long long M);
+/* out (n, M) contiguous, input dtype: every row ascending, NaNs last (the
+ * order of np.sort).  x and out may not overlap.  ws may be null where
+ * ertd_rows_sort_ws_bytes is 0 (rows of one tile).                          */
+int ertd_rows_sort(const void* x, int dtype, int n, long long M, long long ld, void* out,
+                   void* ws, size_t ws_bytes, void* stream);
+size_t ertd_wasserstein_ws_bytes(int dtype, int n, long long Mu, long long Mv);
+/* out (n) float64: W1(row s of u, v); u (n, Mu) pitch ld, v (Mv), same dtype.
+ * scipy's _cdf_distance(p = 1) without weights, term for term: both sides
+ * sorted in their dtype, promoted to float64, and with z the merged sorted
+ * sequence, i_k / j_k the keys of u / v among z[0..k],
+ *   out[s] = sum over k < Mu + Mv - 1 of |i_k / Mu - j_k / Mv| (z[k+1] - z[k])
+ * with two real divisions per term, so each term carries scipy's bits; the
+ * terms are added in a fixed order (chains of at most 64, a term passes
+ * through at most 88 additions).  A NaN in row s makes out[s] NaN, a NaN in
+ * v every out[s].                                                            */
+int ertd_wasserstein(const void* u, int dtype, int n, long long Mu, long long ld,
+                     const void* v, long long Mv, double* out,
+                     void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

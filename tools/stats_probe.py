@@ -1,8 +1,11 @@
-"""Time the ensemble-statistics kernels (csrc/ensstats.hip) at the reference's
-shapes, beside two baselines measured in the same run on the same box:
+"""Time the ensemble-statistics kernels (csrc/ensstats.hip) and the row sort /
+Wasserstein distance (csrc/rowsort.hip) at the reference's shapes, beside two
+baselines measured in the same run on the same box:
 
-  * the reference's numpy formulation on the host, and
-  * a torch.sort + gather composition of the same percentiles on the same GPU.
+  * the reference's numpy / scipy formulation on the host, and
+  * a torch.sort + gather composition of the same percentiles on the same GPU
+    (torch.sort of the same rows; torch.sort + torch.searchsorted for the
+    distance).
 
     python tools/stats_probe.py [--out profiles/stats_probe.json] [--repeats 9] [--inner 20]
 
@@ -123,6 +126,24 @@ def numpy_wsse(sim, obs, A=0.1, B=0.01):
     return out
 
 
+def torch_wasserstein(u, v):
+    """scipy's _cdf_distance(p = 1) of every row of u (n, M) against v, composed
+    of torch.sort and torch.searchsorted."""
+    n = u.shape[0]
+    us, vs = torch.sort(u, dim=1).values, torch.sort(v).values
+    allv = torch.sort(torch.cat([u, v.expand(n, -1)], dim=1), dim=1).values
+    head = allv[:, :-1].contiguous()
+    deltas = allv[:, 1:] - head
+    u_cdf = torch.searchsorted(us, head, right=True).double() / u.shape[1]
+    v_cdf = torch.searchsorted(vs, head, right=True).double() / v.shape[0]
+    return ((u_cdf - v_cdf).abs() * deltas).sum(dim=1)
+
+
+def scipy_wasserstein(sim, obs):
+    from scipy.stats import wasserstein_distance
+    return [wasserstein_distance(s.flatten(), obs.flatten()) for s in sim]
+
+
 def row(name, ours, torch_row, numpy_row, in_bytes, extra=None):
     med = ours["median_us"]
     r = {"name": name, "ertdiff": ours, "torch_sort_composition": torch_row, "numpy_host": numpy_row,
@@ -224,6 +245,47 @@ def main():
                     device_time(lambda: torch_wsse(x, obs), R, I),
                     host_time(lambda: numpy_wsse(xn, on), a.host_repeats), in_bytes + obs.numel() * 8,
                     {"note": "torch row: eager elementwise + mean (no sort in WSSE)"}))
+
+    # row sort and Wasserstein-1 of every realisation against the observation (csrc/rowsort.hip)
+    Mf = M * E
+    xf, of = x.reshape(n, Mf), obs.reshape(Mf)
+    srt = torch.empty(n, Mf, dtype=torch.float64, device=dev)
+    sort_ws = torch.empty(lib.ertd_rows_sort_ws_bytes(1, n, Mf), dtype=torch.uint8, device=dev)
+    w1_ws = torch.empty(lib.ertd_wasserstein_ws_bytes(1, n, Mf, Mf), dtype=torch.uint8, device=dev)
+    w1 = torch.empty(n, dtype=torch.float64, device=dev)
+
+    def sort_dev():
+        _lib.check(lib.ertd_rows_sort(xf.data_ptr(), 1, n, Mf, Mf, srt.data_ptr(), sort_ws.data_ptr(),
+                                      sort_ws.numel(), s), "rows_sort")
+
+    def w1_dev():
+        _lib.check(lib.ertd_wasserstein(xf.data_ptr(), 1, n, Mf, Mf, of.data_ptr(), Mf, w1.data_ptr(),
+                                        w1_ws.data_ptr(), w1_ws.numel(), s), "wasserstein")
+
+    sort_dev()
+    same = bool(torch.equal(srt, torch.sort(xf, dim=1).values))
+    torch_sort = device_time(lambda: torch.sort(xf, dim=1), R, I)
+    rows.append(row("sort_rows (100,65702) f64, device", device_time(sort_dev, R, I), torch_sort, None,
+                    in_bytes, {"equal_torch_sort": same, "note": "torch row: torch.sort(x, dim=1)"}))
+    rows.append(row("sort_rows (100,65702) f64, api", device_time(lambda: ertdiff.sort_rows(xf), R, I),
+                    torch_sort, host_time(lambda: np.sort(xn.reshape(n, Mf), axis=1), a.host_repeats), in_bytes))
+    w1_dev()
+    tw = torch_wasserstein(xf, of)
+    rel = float(((w1 - tw).abs() / tw.abs()).max())
+    try:
+        sp = host_time(lambda: scipy_wasserstein(xn, on), a.host_repeats)
+        sp_rel = float(np.max(np.abs(w1.cpu().numpy() - np.array(scipy_wasserstein(xn, on))) / tw.cpu().numpy()))
+    except ImportError:
+        sp, sp_rel = None, None
+    torch_w1 = device_time(lambda: torch_wasserstein(xf, of), R, I)
+    note = {"max_rel_diff_vs_torch_composition": rel, "max_rel_diff_vs_scipy": sp_rel,
+            "note": "torch row: torch.sort + torch.searchsorted composition; numpy row: scipy's loop over "
+                    "the 100 realisations on the host"}
+    rows.append(row("wasserstein (100,4693,14) vs (4693,14) f64, device", device_time(w1_dev, R, I),
+                    torch_w1, sp, in_bytes + of.numel() * 8, note))
+    rows.append(row("wasserstein (100,4693,14) vs (4693,14) f64, api",
+                    device_time(lambda: ertdiff.wasserstein(x, obs), R, I), torch_w1, sp,
+                    in_bytes + of.numel() * 8))
 
     res = {"device": torch.cuda.get_device_name(0), "library": os.path.basename(_lib.LIB_PATH), "repeats": R, "inner": I, "host_threads": torch.get_num_threads(),
            "hbm_spec_TBps": HBM_SPEC_TBS, "hbm_copy_TBps": HBM_COPY_TBS, "rows": rows}
