@@ -40,10 +40,18 @@ namespace {
 
 inline int rcode(hipError_t e) { return e == hipSuccess ? ERTD_OK : (int)e; }
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float silu_grad(float x) {
   const float s = 1.0f / (1.0f + expf(-x));
   return s * (1.0f + x * (1.0f - s));
+}
+// float64 evaluations, rounded once: the standalone elementwise entry points
+// (small embedding tensors, the im2col fallback's conv input) hold 2 fp32 ulp of
+// the exact value everywhere, including around silu'(x) = 0 at x = -1.278 where
+// the fp32 product form cancels, and in the negative tail of silu
+__device__ __forceinline__ double silu_d(double x) { return x / (1.0 + exp(-x)); }
+__device__ __forceinline__ double silu_grad_d(double x) {
+  const double s = 1.0 / (1.0 + exp(-x));
+  return s * (1.0 + x * (1.0 - s));
 }
 
 // ---- GroupNorm (+SiLU) apply ------------------------------------------------------
@@ -58,9 +66,7 @@ __global__ void gn_act_apply_kernel(const float* __restrict__ xa, int Ca, const 
   const int b = (int)(bc / C), c = (int)(bc - (size_t)b * C);
   const float x = c < Ca ? xa[((size_t)b * Ca + c) * HW + p] : xb[((size_t)b * Cb + c - Ca) * HW + p];
   const float2 g = ss[bc];
-  float v = fmaf(x, g.x, g.y);
-  if (act == ACT_GN_SILU) v = v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-  out[i] = v;
+  out[i] = act == ACT_GN_SILU ? (float)silu_d((double)x * (double)g.x + (double)g.y) : fmaf(x, g.x, g.y);
 }
 
 // ---- GroupNorm (+SiLU) backward: one 256-thread workgroup per (group, sample).
@@ -510,8 +516,8 @@ __global__ void eltwise_kernel(int op, const float* __restrict__ x, const float*
   if (i >= n) return;
   float v;
   switch (op) {
-    case ELT_SILU: v = silu_f(x[i]); break;
-    case ELT_SILU_BWD: v = y[i] * silu_grad(x[i]); break;   // x = pre-activation, y = dL/dout
+    case ELT_SILU: v = (float)silu_d((double)x[i]); break;
+    case ELT_SILU_BWD: v = (float)((double)y[i] * silu_grad_d((double)x[i])); break;   // x = pre-activation, y = dL/dout
     case ELT_RELU: v = fmaxf(x[i], 0.f); break;
     case ELT_RELU_BWD: v = x[i] > 0.f ? y[i] : 0.f; break;
     case ELT_ADD: v = x[i] + y[i]; break;
@@ -749,8 +755,8 @@ int ertd_gn_act_backward_add(const float* x, int Ca, const float* x2, int Cb, in
 
 int ertd_im2col(const float* x, int C, int B, int H, int ks, int mode, float* out, void* stream) {
   if (!x || !out || C < 1 || B < 1 || H < 1 || (ks != 1 && ks != 3) || mode < MODE_S1 ||
-      mode > MODE_UP || (ks == 1 && mode != MODE_S1))
-    return ERTD_EINVAL;
+      mode > MODE_UP || (ks == 1 && mode != MODE_S1) || (mode == MODE_S2 && (H & 1)))
+    return ERTD_EINVAL;   // stride 2: H / 2 output columns is the conv's size for even H only
   const int Ho = mode == MODE_S2 ? H / 2 : (mode == MODE_UP ? 2 * H : H);
   const size_t n = (size_t)B * C * ks * ks * Ho * Ho;
   im2col_kernel<<<nblk(n), 256, 0, (hipStream_t)stream>>>(x, C, H, ks, mode, Ho, n, out);
@@ -991,11 +997,13 @@ int ertd_split(const float* src, float* const* dsts, const long long* sizes, int
 
 int ertd_adam_multi(float* const* params, const float* const* grads, float* const* exp_avg,
                     float* const* exp_avg_sq, const long long* sizes, int ntensors, int step,
-                    float lr, float beta1, float beta2, float eps, void* stream) {
+                    double lr, double beta1, double beta2, double eps, void* stream) {
   if (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || ntensors < 1 || step < 1)
     return ERTD_EINVAL;
-  const double bc1 = 1.0 - std::pow((double)beta1, step);
-  const double bc2 = 1.0 - std::pow((double)beta2, step);
+  // the hyperparameters arrive as the optimizer holds them (Python floats = doubles):
+  // from an fp32 argument 1 - (double)0.999f is 1.3e-5 below 1 - 0.999, and exp_avg_sq with it
+  const double bc1 = 1.0 - std::pow(beta1, step);
+  const double bc2 = 1.0 - std::pow(beta2, step);
   hipStream_t s = (hipStream_t)stream;
   for (int t0 = 0; t0 < ntensors; t0 += ADAM_T) {
     AdamMulti a{};
@@ -1014,12 +1022,12 @@ int ertd_adam_multi(float* const* params, const float* const* grads, float* cons
     a.boff[a.nt] = (int)blocks;
     if (blocks == 0) continue;
     // scalars formed as torch does: Python floats (double), rounded when applied to fp32
-    a.one_minus_b1 = (float)(1.0 - (double)beta1);
-    a.b2 = beta2;
-    a.one_minus_b2 = (float)(1.0 - (double)beta2);
-    a.step_size_neg = (float)(-((double)lr / bc1));
+    a.one_minus_b1 = (float)(1.0 - beta1);
+    a.b2 = (float)beta2;
+    a.one_minus_b2 = (float)(1.0 - beta2);
+    a.step_size_neg = (float)(-(lr / bc1));
     a.bc2_sqrt = (float)std::sqrt(bc2);
-    a.eps = eps;
+    a.eps = (float)eps;
     adam_multi_kernel<<<(unsigned)blocks, 256, 0, s>>>(a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;

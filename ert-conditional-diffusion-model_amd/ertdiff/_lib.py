@@ -168,7 +168,8 @@ SIGNATURES = {
     "ertd_encoder_train_ws_bytes": (_SZ, [_I, _I]),
     "ertd_encoder_train_fwd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _SZ, _VP]),
     "ertd_encoder_train_bwd": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
-    "ertd_adam_multi": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _F, _F, _F, _F, _VP]),
+    "ertd_adam_multi": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, ctypes.c_double, ctypes.c_double,
+                             ctypes.c_double, ctypes.c_double, _VP]),
     "ertd_unet_plan_launch": (_I, [_VP, _VP]),
     "ertd_unet_plan_launch_steps": (_I, [_VP, _I, _VP]),
     "ertd_unet_plan_destroy": (_I, [_VP]),

@@ -467,7 +467,8 @@ int ertd_unet_plan_destroy(ertd_unet_plan* plan);
  *   gradient, addc (B, C, HW) in the concatenated channel order (a ResBlock's skip / identity
  *   gradient of the same input), added first (as a separate add before the call would); csum
  *   optional (null: none), and when given it sums the GroupNorm term only.
- * ertd_im2col: out (B, C*ks*ks, Ho*Ho) patches of x (B, C, H, H), mode 0 s1 / 1 s2 / 2 upsample.
+ * ertd_im2col: out (B, C*ks*ks, Ho*Ho) patches of x (B, C, H, H), mode 0 s1 / 1 s2 (even H,
+ *   Ho = H / 2) / 2 upsample.
  * ertd_wgrad_gemm: dW (M, N) = sum_b dY_b (M, P) . X_b (N, P)^T (batch strides bsA, bsB),
  *   fp32 MFMA, split per sample + fixed-order reduction; ws >= ertd_wgrad_ws_bytes.
  * ertd_conv_weight_flip: out (Cin, Cout, ks, ks) = w (Cout, Cin, ks, ks) spatially flipped.
@@ -487,7 +488,8 @@ int ertd_unet_plan_destroy(ertd_unet_plan* plan);
  *   ws >= ertd_mse_loss_ws_bytes() (float64 partial sums, caller-owned).
  * ertd_encoder_train_fwd / _bwd: the reference condition encoder (:133-142) with saved
  *   activations in ws (pool mean m (B, 64) out) / conv-parameter grads from g = dL/dm / L.
- * ertd_adam_multi: torch.optim.Adam step (no weight decay) over ntensors tensors.        */
+ * ertd_adam_multi: torch.optim.Adam step (no weight decay) over ntensors tensors; lr, betas
+ *   and eps as doubles (the optimizer's Python floats: 1 - beta2 is formed in double).  */
 int ertd_gn_stats_mr(const float* x, int Ca, const float* x2, int Cb, int B, int HW, int groups,
                      const float* gamma, const float* beta, float* ss_out, float* mr_out,
                      void* stream);
@@ -613,7 +615,7 @@ int ertd_encoder_train_bwd(const float* packed, const float* cond, const float* 
                            size_t ws_bytes, void* stream);
 int ertd_adam_multi(float* const* params, const float* const* grads, float* const* exp_avg,
                     float* const* exp_avg_sq, const long long* sizes, int ntensors, int step,
-                    float lr, float beta1, float beta2, float eps, void* stream);
+                    double lr, double beta1, double beta2, double eps, void* stream);
 
 /* ---- Ensemble KDE mode (csrc/kde.hip) -------------
  * Replaces the reference's per-cell loop ERT_Conditional_Diffusion.py:747-762
