@@ -581,4 +581,57 @@ int ertd_train_steps_dev(const ertd_weights* w, const float* x0, int64_t* t, flo
   return ERTD_OK;
 }
 
+int ertd_train_epoch_dev(const ertd_weights* w, const float* x0_all, const float* cond_all,
+                         long long n_data, const int32_t* rows, int n_rows, int64_t* t_all,
+                         float* noise_all, const float* alpha_bar, int B, int L, const float* freq,
+                         float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                         int* step_dev, const float* adam_table, int table_first, int table_len,
+                         int draw, int T, uint64_t seed, float* losses, void* ws, size_t ws_bytes,
+                         void* stream) {
+  if (n_rows < 1 || B < 1 || n_data < 1 || !rows) return ERTD_EINVAL;
+  const int r = train_step_args_ok(w, x0_all, t_all, noise_all, cond_all, alpha_bar, B, L, freq, grads,
+                                   exp_avg, exp_avg_sq, losses, ws, ws_bytes);
+  if (r != ERTD_OK) return r;
+  if (!step_dev || !adam_table || table_first < 1 || table_len < 1) return ERTD_EINVAL;
+  if (draw && T < 1) return ERTD_EINVAL;
+  const TrainAdam adam{0, 0.f, 0.f, 0.f, 0.f, adam_table, step_dev, table_first, table_len, seed,
+                       draw ? 1 : 0, T};
+  const size_t P = (size_t)w->param_dim;
+  // batch i: rows [i*B, min((i+1)*B, n_rows)) -- the last one with its own,
+  // smaller B (its workspace layout fits inside the one sized for B)
+  for (int i0 = 0, i = 0; i0 < n_rows; i0 += B, ++i) {
+    const int Bi = n_rows - i0 < B ? n_rows - i0 : B;
+    const int e = rc(launch_train_step(*w, x0_all, t_all + i0, noise_all + (size_t)i0 * P, cond_all,
+                                       alpha_bar, Bi, L, freq, grads, exp_avg, exp_avg_sq, adam,
+                                       losses + i, (float*)ws, (hipStream_t)stream, rows + i0));
+    if (e != ERTD_OK) return e;
+  }
+  return ERTD_OK;
+}
+
+int ertd_validation_epoch_dev(const ertd_weights* w, const float* x0_all, const float* cond_all,
+                              long long n_data, const int32_t* rows, int n_rows, int64_t* t_all,
+                              float* noise_all, const float* alpha_bar, int B, int L,
+                              const float* freq, const int* ctr, int draw, int T, uint64_t seed,
+                              float* eps_all, float* losses, void* ws, size_t ws_bytes,
+                              void* stream) {
+  if (n_rows < 1 || B < 1 || n_data < 1 || L < 1) return ERTD_EINVAL;
+  if (!weights_ok(w) || !x0_all || !cond_all || !rows || !t_all || !noise_all || !alpha_bar || !freq ||
+      !eps_all || !losses || !ws)
+    return ERTD_EINVAL;
+  if (draw && (!ctr || T < 1)) return ERTD_EINVAL;
+  if (train_ws_floats(B, L) * sizeof(float) > ws_bytes) return ERTD_ENOSPC;
+  const size_t P = (size_t)w->param_dim;
+  for (int i0 = 0, i = 0; i0 < n_rows; i0 += B, ++i) {
+    const int Bi = n_rows - i0 < B ? n_rows - i0 : B;
+    const int e = rc(launch_validation_batch(*w, x0_all, cond_all, rows + i0, t_all + i0,
+                                             noise_all + (size_t)i0 * P, alpha_bar, Bi, L, freq,
+                                             draw ? ctr + i : nullptr, T, seed,
+                                             eps_all + (size_t)i0 * P, losses + i, (float*)ws,
+                                             (hipStream_t)stream));
+    if (e != ERTD_OK) return e;
+  }
+  return ERTD_OK;
+}
+
 }  // extern "C"

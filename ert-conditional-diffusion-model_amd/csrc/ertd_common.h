@@ -321,7 +321,17 @@ hipError_t launch_train_step(const ertd_weights& w, const float* x0, const int64
                              const float* noise, const float* cond, const float* alpha_bar, int B,
                              int L, const float* freq, float* const* grads, float* const* exp_avg,
                              float* const* exp_avg_sq, const TrainAdam& adam, float* loss_out,
-                             float* ws, hipStream_t s);
+                             float* ws, hipStream_t s, const int* rows = nullptr);
+// rows (B): member b reads x0 row rows[b] / cond row rows[b] of a resident
+// dataset (an epoch step, ertd_train_epoch_dev); everything else -- workspace
+// rows, t / noise, the Philox key -- stays keyed by the batch position b.
+// One forward-only batch on such rows: eps, the batch's MSE; ctr (device, 1):
+// the head draws t / noise keyed (seed, member, *ctr) into t / noise
+hipError_t launch_validation_batch(const ertd_weights& w, const float* x0, const float* cond,
+                                   const int* rows, int64_t* t, float* noise, const float* alpha_bar,
+                                   int B, int L, const float* freq, const int* ctr, int T,
+                                   uint64_t seed, float* eps_out, float* loss_out, float* ws,
+                                   hipStream_t s);
 hipError_t launch_adam(const ertd_weights& w, float* const* grads, float* const* exp_avg,
                        float* const* exp_avg_sq, int step, float lr, float beta1, float beta2,
                        float eps, hipStream_t s);

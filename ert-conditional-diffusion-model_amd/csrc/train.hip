@@ -93,8 +93,8 @@ static_assert(NG1 + NG2 == NG, "split rows cover the gradient row");
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void enc_train_kernel(
     const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ w2,
-    const float* __restrict__ b2, const float* __restrict__ cond, int L, int L1, int L2, int S,
-    float* __restrict__ partial, float* __restrict__ a1s, uint32_t* __restrict__ m2w,
+    const float* __restrict__ b2, const float* __restrict__ cond, const int* __restrict__ rows, int L,
+    int L1, int L2, int S, float* __restrict__ partial, float* __restrict__ a1s, uint32_t* __restrict__ m2w,
     unsigned* __restrict__ fin_cnt, int* __restrict__ step_ctr, ertd_weights wd,
     float* __restrict__ wt, float* __restrict__ w2b) {
   __shared__ __attribute__((aligned(16))) EncSmem sm;
@@ -168,7 +168,9 @@ __global__ __launch_bounds__(256) void enc_train_kernel(
       }
     }
   }
-  stage_cond_f32(sm.X, cond + (size_t)b * CIN * L, L, 4 * j0 - 3, tid);
+  // member b's condition is row rows[b] of a resident dataset (an epoch step), or row b
+  const size_t row = rows ? (size_t)rows[b] : (size_t)b;
+  stage_cond_f32(sm.X, cond + row * CIN * L, L, 4 * j0 - 3, tid);
   __syncthreads();
   // conv1 fragment s of lane (o = l32, h): W1[o][c = s/3 + 7h][s % 3], contiguous in s
   float wa[STEPS1];
@@ -399,7 +401,7 @@ struct HeadBwdW {
 template <bool PRE>
 __device__ __forceinline__ void head_forward(
     const ertd_weights& w, const float* __restrict__ wt, const float* __restrict__ x_in,
-    const float* __restrict__ x0, const float* __restrict__ noise,
+    const float* __restrict__ x0, const int* __restrict__ rows, const float* __restrict__ noise,
     const float* __restrict__ alpha_bar, const int64_t* __restrict__ t_vec,
     const float* __restrict__ freq, const float* __restrict__ partial, int S, int L2,
     float* __restrict__ V, float* __restrict__ eps_out, HeadRng rng, HeadSmem& s, int b,
@@ -441,7 +443,8 @@ __device__ __forceinline__ void head_forward(
     if (x_in) x0v = x_in[(size_t)b * P + tid];
     else {
       ab = alpha_bar[tme];
-      x0v = x0[(size_t)b * P + tid];
+      const size_t row = rows ? (size_t)rows[b] : (size_t)b;   // x0 row of a resident dataset
+      x0v = x0[row * P + tid];
     }
     be = w.mlp2_b[tid];
   }
@@ -751,9 +754,9 @@ __device__ __forceinline__ void conv_bwd_images(SM& sm, const float* __restrict_
 // else the chain alone, rows [dW1 | db1] of NG1 (the reference train step)
 template <bool W2>
 __global__ __launch_bounds__(256, 3) void conv_bwd_kernel(
-    const float* __restrict__ w2b, const float* __restrict__ cond, const float* __restrict__ a1s,
-    const uint32_t* __restrict__ m2w, const float* __restrict__ g, int g_stride, int L, int L1,
-    int L2, int S, float* __restrict__ gpart, int c1, int c2) {
+    const float* __restrict__ w2b, const float* __restrict__ cond, const int* __restrict__ rows,
+    const float* __restrict__ a1s, const uint32_t* __restrict__ m2w, const float* __restrict__ g,
+    int g_stride, int L, int L1, int L2, int S, float* __restrict__ gpart, int c1, int c2) {
   __shared__ __attribute__((aligned(16))) ConvBwdSmem sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l32 = lane & 31;
@@ -791,7 +794,7 @@ __global__ __launch_bounds__(256, 3) void conv_bwd_kernel(
     for (int s = 0; s < 32; ++s) wt1[s] = oddw ? base[(2 * 32 + s) * 64] : 0.f;
   }
   // ---- the cond strip (phase B's image), loaded now, stored after phase A
-  const float* cb = cond + (size_t)b * CIN * L;
+  const float* cb = cond + (rows ? (size_t)rows[b] : (size_t)b) * CIN * L;   // the forward's row
   const int pos = 4 * j0 - 3 + tid;
   const bool cin = pos >= 0 && pos < L;
   float cv[CIN];
@@ -1065,7 +1068,7 @@ struct W2mArgs {
 template <int MODE>
 __global__ __launch_bounds__(HT) void train_head_kernel(
     ertd_weights w, const float* __restrict__ wt, const float* __restrict__ x_in,
-    const float* __restrict__ x0, const float* __restrict__ noise,
+    const float* __restrict__ x0, const int* __restrict__ rows, const float* __restrict__ noise,
     const float* __restrict__ alpha_bar, const int64_t* __restrict__ t_vec,
     const float* __restrict__ freq, const float* __restrict__ partial, int S, int L2,
     float* __restrict__ vec, float* __restrict__ eps_out, const float* __restrict__ dout_in,
@@ -1083,8 +1086,8 @@ __global__ __launch_bounds__(HT) void train_head_kernel(
   float* V = vec + (size_t)b * TV;
   HeadBwdW bw;
   if constexpr (MODE != 1)
-    head_forward<MODE == 2>(w, wt, x_in, x0, noise, alpha_bar, t_vec, freq, partial, S, L2, V, eps_out, rng,
-                            s, b, tid, bw);
+    head_forward<MODE == 2>(w, wt, x_in, x0, rows, noise, alpha_bar, t_vec, freq, partial, S, L2, V,
+                            eps_out, rng, s, b, tid, bw);
   if constexpr (MODE == 2) {
     __syncthreads(); HSTAMP(17);
     head_backward(w, wt, dout_in, s.nz, two_over_n, L2, V, dx_out, s.eps, s.h, s.hc, s, b, tid, bw, true);
@@ -1455,6 +1458,34 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// MSELoss(mean) of a forward-only (validation) batch, in the train step's
+// order: per member the squared errors summed over o (head_backward), the
+// members added in b order and the sum times inv_n (train_final_kernel).  One
+// block; the member sums go through the members' saved rows (vec[b][TV_SQ]).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mse_rows_kernel(const float* __restrict__ eps,
+                                                       const float* __restrict__ noise, int B, int P,
+                                                       float inv_n, float* vec, float* __restrict__ loss) {
+  const int tid = threadIdx.x;
+  for (int b = tid; b < B; b += 256) {
+    const float* e = eps + (size_t)b * P;
+    const float* z = noise + (size_t)b * P;
+    float acc = 0.f;
+    for (int o = 0; o < P; ++o) {
+      const float diff = e[o] - z[o];
+      acc += diff * diff;
+    }
+    vec[(size_t)b * TV + TV_SQ] = acc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float acc = 0.f;
+    for (int b = 0; b < B; ++b) acc += vec[(size_t)b * TV + TV_SQ];
+    *loss = acc * inv_n;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------
 namespace {
@@ -1553,11 +1584,11 @@ void set_dense(FinalArgs& a, const ertd_weights& w, const TrainWs& W, int B, flo
 
 // wd: the model's dense weights (their k-major copies go to W.wt), or null
 hipError_t launch_enc(const float* w1, const float* b1, const float* w2, const float* b2,
-                      const float* cond, int B, int L, const TrainWs& W, int* step_ctr,
-                      const ertd_weights* wd, hipStream_t s) {
+                      const float* cond, const int* rows, int B, int L, const TrainWs& W,
+                      int* step_ctr, const ertd_weights* wd, hipStream_t s) {
   const int L1 = conv_len(L), L2 = conv_len(L1), S = n_strips(L2);
-  enc_train_kernel<<<dim3((unsigned)(B * S)), 256, 0, s>>>(w1, b1, w2, b2, cond, L, L1, L2, S, W.partial,
-                                                         W.a1s, W.m2w, W.cnt, step_ctr,
+  enc_train_kernel<<<dim3((unsigned)(B * S)), 256, 0, s>>>(w1, b1, w2, b2, cond, rows, L, L1, L2, S,
+                                                         W.partial, W.a1s, W.m2w, W.cnt, step_ctr,
                                                          wd ? *wd : ertd_weights{}, wd ? W.wt : nullptr,
                                                          W.w2b);
   return hipGetLastError();
@@ -1565,17 +1596,18 @@ hipError_t launch_enc(const float* w1, const float* b1, const float* w2, const f
 
 // (the W2 fragments are the ones the forward on this workspace wrote)
 // w2: with the dW2 work (rows of NG); else the chain alone (rows of NG1)
-hipError_t launch_conv_bwd(const float* cond, const TrainWs& W, const float* g, int g_stride, int B,
-                           int L, bool w2, hipStream_t s) {
+// rows: the forward's row index (null: member b reads row b)
+hipError_t launch_conv_bwd(const float* cond, const int* rows, const TrainWs& W, const float* g,
+                           int g_stride, int B, int L, bool w2, hipStream_t s) {
   const int L1 = conv_len(L), L2 = conv_len(L1), S = n_strips(L2);
   const int nit = B * S, cus = device_cu_count();
   const int c1 = nit < 2 * cus ? nit : 2 * cus, c2 = nit < cus ? nit : cus;
   if (w2)
     conv_bwd_kernel<true><<<dim3((unsigned)((CBW_ABL & 16) ? nit : 2 * nit)), 256, 0, s>>>(
-        W.w2b, cond, W.a1s, W.m2w, g, g_stride, L, L1, L2, S, W.gpart, c1, c2);
+        W.w2b, cond, rows, W.a1s, W.m2w, g, g_stride, L, L1, L2, S, W.gpart, c1, c2);
   else
-    conv_bwd_kernel<false><<<dim3((unsigned)nit), 256, 0, s>>>(W.w2b, cond, W.a1s, W.m2w, g, g_stride,
-                                                              L, L1, L2, S, W.gpart, c1, c2);
+    conv_bwd_kernel<false><<<dim3((unsigned)nit), 256, 0, s>>>(W.w2b, cond, rows, W.a1s, W.m2w, g,
+                                                              g_stride, L, L1, L2, S, W.gpart, c1, c2);
   return hipGetLastError();
 }
 
@@ -1598,7 +1630,7 @@ size_t train_ws_floats(int B, int L) { return ws_layout(B, L, true, nullptr, nul
 hipError_t launch_train_conv_backward(const float* cond, int B, int L, float* ws, hipStream_t s) {
   TrainWs W;
   ws_layout(B, L, true, ws, &W);
-  return launch_conv_bwd(cond, W, W.vec + TV_G, TV, B, L, false, s);
+  return launch_conv_bwd(cond, nullptr, W, W.vec + TV_G, TV, B, L, false, s);
 }
 
 void adam_table_host(int step_first, int n, float lr, float beta1, float beta2, float eps,
@@ -1616,10 +1648,12 @@ hipError_t launch_train_forward(const ertd_weights& w, const float* x_in, const 
   TrainWs W;
   ws_layout(B, L, true, ws, &W);
   const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
-  hipError_t e = launch_enc(w.enc0_w, w.enc0_b, w.enc2_w, w.enc2_b, cond, B, L, W, nullptr, &w, s);
+  hipError_t e =
+      launch_enc(w.enc0_w, w.enc0_b, w.enc2_w, w.enc2_b, cond, nullptr, B, L, W, nullptr, &w, s);
   if (e != hipSuccess) return e;
-  train_head_kernel<0><<<B, HT, 0, s>>>(w, W.wt, x_in, x0, noise, alpha_bar, t, freq, W.partial, S, L2,
-                                        W.vec, eps_out, nullptr, 0.f, nullptr, HeadRng{}, W2mArgs{});
+  train_head_kernel<0><<<B, HT, 0, s>>>(w, W.wt, x_in, x0, nullptr, noise, alpha_bar, t, freq, W.partial,
+                                        S, L2, W.vec, eps_out, nullptr, 0.f, nullptr, HeadRng{},
+                                        W2mArgs{});
   return hipGetLastError();
 }
 
@@ -1631,12 +1665,13 @@ hipError_t launch_train_backward(const ertd_weights& w, const float* dout, const
   const int P = w.param_dim;
   const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
   const float two_over_n = (float)(2.0 / ((double)B * P));
-  train_head_kernel<1><<<head_grid(B, L), HT, 0, s>>>(w, W.wt, nullptr, nullptr, noise, nullptr, nullptr,
-                                                      nullptr, nullptr, S, L2, W.vec, nullptr, dout,
-                                                      two_over_n, dx_out, HeadRng{}, w2m_args(W, B));
+  train_head_kernel<1><<<head_grid(B, L), HT, 0, s>>>(w, W.wt, nullptr, nullptr, nullptr, noise, nullptr,
+                                                      nullptr, nullptr, nullptr, S, L2, W.vec, nullptr,
+                                                      dout, two_over_n, dx_out, HeadRng{},
+                                                      w2m_args(W, B));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = launch_conv_bwd(cond, W, W.vec + TV_G, TV, B, L, false, s);
+  e = launch_conv_bwd(cond, nullptr, W, W.vec + TV_G, TV, B, L, false, s);
   if (e != hipSuccess) return e;
   FinalArgs a = final_args(W, B * S);
   set_dense(a, w, W, B, grads, loss_out);
@@ -1648,7 +1683,7 @@ hipError_t launch_train_step(const ertd_weights& w, const float* x0, const int64
                              const float* noise, const float* cond, const float* alpha_bar, int B,
                              int L, const float* freq, float* const* grads, float* const* exp_avg,
                              float* const* exp_avg_sq, const TrainAdam& adam, float* loss_out,
-                             float* ws, hipStream_t s) {
+                             float* ws, hipStream_t s, const int* rows) {
   TrainWs W;
   ws_layout(B, L, true, ws, &W);
 
@@ -1656,7 +1691,7 @@ hipError_t launch_train_step(const ertd_weights& w, const float* x0, const int64
   const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
   const float two_over_n = (float)(2.0 / ((double)B * P));
   hipError_t e =
-      launch_enc(w.enc0_w, w.enc0_b, w.enc2_w, w.enc2_b, cond, B, L, W, adam.step_dev, &w, s);
+      launch_enc(w.enc0_w, w.enc0_b, w.enc2_w, w.enc2_b, cond, rows, B, L, W, adam.step_dev, &w, s);
   if (e != hipSuccess) return e;
   HeadRng rng{};
   if (adam.draw) {
@@ -1666,12 +1701,12 @@ hipError_t launch_train_step(const ertd_weights& w, const float* x0, const int64
     rng.t_out = const_cast<int64_t*>(t);
     rng.noise_out = const_cast<float*>(noise);
   }
-  train_head_kernel<2><<<head_grid(B, L), HT, 0, s>>>(w, W.wt, nullptr, x0, noise, alpha_bar, t, freq,
-                                                      W.partial, S, L2, W.vec, nullptr, nullptr,
+  train_head_kernel<2><<<head_grid(B, L), HT, 0, s>>>(w, W.wt, nullptr, x0, rows, noise, alpha_bar, t,
+                                                      freq, W.partial, S, L2, W.vec, nullptr, nullptr,
                                                       two_over_n, nullptr, rng, w2m_args(W, B));
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = launch_conv_bwd(cond, W, W.vec + TV_G, TV, B, L, false, s);
+  e = launch_conv_bwd(cond, rows, W, W.vec + TV_G, TV, B, L, false, s);
   if (e != hipSuccess) return e;
   FinalArgs a = final_args(W, B * S);
   set_dense(a, w, W, B, grads, loss_out);
@@ -1692,6 +1727,38 @@ hipError_t launch_train_step(const ertd_weights& w, const float* x0, const int64
   return launch_final(a, true, s);
 }
 
+// One validation batch (:327-336): the train forward on rows[0 .. B) of a
+// resident dataset, eps to eps_out, and the batch's mean-squared error.  With
+// ctr the head draws t / noise itself, keyed (seed, member, *ctr).  No
+// backward: no parameter, gradient or Adam state is touched.
+hipError_t launch_validation_batch(const ertd_weights& w, const float* x0, const float* cond,
+                                   const int* rows, int64_t* t, float* noise, const float* alpha_bar,
+                                   int B, int L, const float* freq, const int* ctr, int T,
+                                   uint64_t seed, float* eps_out, float* loss_out, float* ws,
+                                   hipStream_t s) {
+  TrainWs W;
+  ws_layout(B, L, true, ws, &W);
+  const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
+  hipError_t e = launch_enc(w.enc0_w, w.enc0_b, w.enc2_w, w.enc2_b, cond, rows, B, L, W, nullptr, &w, s);
+  if (e != hipSuccess) return e;
+  HeadRng rng{};
+  if (ctr) {
+    rng.seed = seed;
+    rng.step = ctr;
+    rng.T = T;
+    rng.t_out = t;
+    rng.noise_out = noise;
+  }
+  train_head_kernel<0><<<B, HT, 0, s>>>(w, W.wt, nullptr, x0, rows, noise, alpha_bar, t, freq, W.partial,
+                                        S, L2, W.vec, eps_out, nullptr, 0.f, nullptr, rng, W2mArgs{});
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int P = w.param_dim;
+  mse_rows_kernel<<<1, 256, 0, s>>>(eps_out, noise, B, P, (float)(1.0 / ((double)B * P)), W.vec,
+                                    loss_out);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // The reference condition encoder alone with saved activations (the U-Net
 // train step's condition branch, unet_train.hip): the same kernels on the raw
@@ -1705,7 +1772,7 @@ hipError_t launch_encoder_train(const float* w1, const float* b1, const float* w
   TrainWs W;
   ws_layout(B, L, false, ws, &W);
   *partial_out = W.partial;
-  return launch_enc(w1, b1, w2, b2, cond, B, L, W, nullptr, nullptr, s);
+  return launch_enc(w1, b1, w2, b2, cond, nullptr, B, L, W, nullptr, nullptr, s);
 }
 
 hipError_t launch_encoder_conv_backward(const float* w2, const float* cond, const float* g, int B,
@@ -1715,7 +1782,7 @@ hipError_t launch_encoder_conv_backward(const float* w2, const float* cond, cons
   ws_layout(B, L, false, ws, &W);
   const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
   (void)w2;  // the fragments of the forward on this workspace
-  hipError_t e = launch_conv_bwd(cond, W, g, C2, B, L, true, s);
+  hipError_t e = launch_conv_bwd(cond, nullptr, W, g, C2, B, L, true, s);
   if (e != hipSuccess) return e;
   FinalArgs a = final_args(W, B * S);
   a.grad[0] = dw1;

@@ -6,13 +6,14 @@ compute runs in hand-written HIP kernels (libertdiff_hip.so, C ABI in
 include/ertdiff.h).  There is no CPU fallback: device work on a non-gfx950
 device raises.
 """
-from .data import (DiffusionDataset, bounds_mask, check_param_bounds, inverse_transform,
+from .data import (DeviceDataset, DiffusionDataset, bounds_mask, check_param_bounds, inverse_transform,
                    load_best_model, save_checkpoint, transform_to_unconstrained)
 from .model import STATE_KEYS, ConditionalDiffusionModel, get_timestep_embedding, q_sample
 from .sampler import (SamplerPlan, as_ertdiff_model, draw_reference_noise, philox_normal,
                       sample_conditions, sample_model)
 from .schedule import get_diffusion_schedule, step_tables, timestep_frequencies
-from .train import DiffusionForwardFn, TrainPlan, train_step, validation_loss
+from .train import (DiffusionForwardFn, TrainPlan, ValidationPlan, epoch_loss, fit, train_step,
+                    validation_loss)
 from .ensemble import member_range, sample_conditions_sharded, sample_ensemble
 from .postproc import compact, postprocess, sample_realisations
 from .unet import ConditionalUNet, UNetSamplerPlan, sample_unet
@@ -37,4 +38,5 @@ __all__ = [
     "coverage_from_counts", "interval_fractions", "parameter_uncertainty_metrics", "wsse", "WSSE_metric",
     "avg_prop_indicator_function", "accuracy_score", "preccision_score", "goodness_score",
     "uncertainty_metrics", "sort_rows", "wasserstein", "wasserstein_distance", "mse",
+    "DeviceDataset", "ValidationPlan", "epoch_loss", "fit",
 ]

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
+from torch.utils.data import Dataset, Subset
 
 _EPS = 1e-6
 
@@ -56,6 +56,52 @@ class DiffusionDataset(Dataset):
 
     def __getitem__(self, idx):
         return self.params[idx], self.conditions[idx]
+
+
+class DeviceDataset:
+    """The whole dataset resident on one device: x0 (N, P) and cond (N, 14, L)
+    as contiguous float32 tensors.  TrainPlan.run_epoch / ValidationPlan.run read
+    their batches out of it through a row index, so an epoch needs no
+    per-batch gather or copy (the reference's 5076 x 14 x 4693 floats are
+    1.33 GB).  Works on CPU tensors too (nothing here launches a kernel)."""
+
+    def __init__(self, x0: torch.Tensor, cond: torch.Tensor):
+        if x0.dtype != torch.float32 or cond.dtype != torch.float32:
+            raise RuntimeError(f"ertdiff: DeviceDataset holds float32 (got {x0.dtype}, {cond.dtype})")
+        if x0.dim() != 2 or cond.dim() != 3 or cond.shape[0] != x0.shape[0] or cond.shape[1] != 14:
+            raise RuntimeError("ertdiff: DeviceDataset takes x0 (N, P) and cond (N, 14, L), got "
+                               f"{tuple(x0.shape)} and {tuple(cond.shape)}")
+        if x0.device != cond.device:
+            raise RuntimeError(f"ertdiff: x0 on {x0.device}, cond on {cond.device}")
+        self.x0 = x0.contiguous()
+        self.cond = cond.contiguous()
+
+    def __len__(self):
+        return self.x0.shape[0]
+
+    @property
+    def device(self):
+        return self.x0.device
+
+    @classmethod
+    def from_dataset(cls, ds, device=None):
+        """Stack a DiffusionDataset, or a torch.utils.data.Subset of one (nested
+        subsets too), once: row i is bitwise what ds[i] returns, and the
+        transposed (non-contiguous) ERT view is made contiguous."""
+        idx = None
+        while isinstance(ds, Subset):
+            sub = torch.as_tensor(ds.indices, dtype=torch.int64)
+            idx = sub if idx is None else sub[idx]
+            ds = ds.dataset
+        if not isinstance(ds, DiffusionDataset):
+            raise RuntimeError("ertdiff: DeviceDataset.from_dataset takes a DiffusionDataset or a "
+                               f"Subset of one, got {type(ds).__name__}")
+        x0, cond = ds.params, ds.conditions
+        if idx is not None:
+            x0, cond = x0[idx], cond[idx]
+        if device is not None:   # the copy is made contiguous on the host first: one plain transfer
+            x0, cond = x0.contiguous().to(device), cond.contiguous().to(device)
+        return cls(x0, cond)
 
 
 def bounds_mask(param: np.ndarray, limits: np.ndarray) -> np.ndarray:

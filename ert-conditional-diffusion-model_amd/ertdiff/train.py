@@ -15,6 +15,14 @@
                        device): the reference loop's 63,500 steps at one graph
                        launch each.
   validation_loss      the no-grad validation pass body (:327-336).
+  TrainPlan.run_epoch  one whole epoch (:308-320) as ONE graph replay: the train
+                       kernels read each batch out of a device-resident
+                       DeviceDataset through a row index (no gather, no copy, no
+                       per-step call boundary, no host sync), the partial last
+                       batch included; per-batch losses stay on the device.
+  ValidationPlan       the validation pass (:325-338) the same way, forward only.
+  epoch_loss           the reference's size-weighted epoch mean (:320-322, :336-338).
+  fit                  the loop of :305-356 on those three.
 """
 from __future__ import annotations
 
@@ -154,6 +162,83 @@ def train_step(model, optimizer, x0, cond, T, alpha_bar, *, t=None, noise=None,
     return loss if return_tensor else loss.item()
 
 
+def batch_sizes(n_rows: int, B: int):
+    """The batch sizes DataLoader(batch_size=B, drop_last=False) yields over
+    n_rows items: n_rows // B full batches, then the remainder if any."""
+    n_rows, B = int(n_rows), int(B)
+    return [B] * (n_rows // B) + ([n_rows % B] if n_rows % B else [])
+
+
+def _epoch_order(order, n_data: int, B: int, drop_last: bool):
+    """The epoch's row indices, checked on the host side BEFORE any launch (the
+    device cannot report a bad index): (order, n_rows)."""
+    if not isinstance(order, torch.Tensor):
+        order = torch.as_tensor(order)
+    if order.dtype.is_floating_point or order.dtype.is_complex or order.dtype == torch.bool:
+        raise RuntimeError(f"ertdiff: the epoch order must be an integer tensor, got {order.dtype}")
+    if order.dim() != 1:
+        raise RuntimeError(f"ertdiff: the epoch order must be 1-D, got {tuple(order.shape)}")
+    n = order.numel()
+    if drop_last:
+        n = n // B * B
+        order = order[:n]
+    if n == 0:
+        raise RuntimeError("ertdiff: the epoch order is empty")
+    lo, hi = torch.aminmax(order)
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi >= n_data:
+        raise IndexError(f"ertdiff: row index {lo if lo < 0 else hi} out of range [0, {n_data})")
+    return order, n
+
+
+def _check_data(data, dev, L: int, P: int):
+    from .data import DeviceDataset
+    if not isinstance(data, DeviceDataset):
+        raise RuntimeError(f"ertdiff: expected a DeviceDataset, got {type(data).__name__}")
+    x0, cond = data.x0, data.cond
+    if x0.dtype != torch.float32 or cond.dtype != torch.float32:
+        raise RuntimeError("ertdiff: the dataset must be float32")
+    if not (x0.is_contiguous() and cond.is_contiguous()):
+        raise RuntimeError("ertdiff: the dataset tensors must be contiguous")
+    if x0.device != dev or cond.device != dev:
+        raise RuntimeError(f"ertdiff: the dataset is on {x0.device}, the plan on {dev}")
+    if x0.dim() != 2 or x0.shape[1] != P:
+        raise RuntimeError(f"ertdiff: this plan takes x0 rows of {P} parameters, got {tuple(x0.shape)}")
+    if cond.dim() != 3 or cond.shape[0] != x0.shape[0] or tuple(cond.shape[1:]) != (_lib.CIN, L):
+        raise RuntimeError(f"ertdiff: this plan was captured for conditions (N, {_lib.CIN}, {L}), got "
+                           f"{tuple(cond.shape)}")
+
+
+def _check_draws(t, noise, n: int, P: int, n_alpha: int, what: str):
+    """t / noise of a whole epoch: both or neither; True when the device draws."""
+    if (t is None) != (noise is None):
+        raise RuntimeError(f"ertdiff: {what} takes both t and noise, or neither")
+    if t is None:
+        return True
+    if tuple(t.shape) != (n,) or tuple(noise.shape) != (n, P):
+        raise RuntimeError(f"ertdiff: {what} takes t of shape ({n},) and noise of shape ({n}, {P})")
+    if noise.dtype != torch.float32:
+        raise RuntimeError(f"ertdiff: noise must be float32, got {noise.dtype}")
+    tl = t.to(torch.int64)
+    if int(tl.min()) < 0 or int(tl.max()) >= n_alpha:
+        raise IndexError(f"ertdiff: t out of range [0, {n_alpha})")
+    return False
+
+
+class _EpochBufs:
+    """The fixed buffers an epoch graph of n_rows rows addresses."""
+
+    def __init__(self, n: int, B: int, P: int, dev, with_eps: bool = False):
+        nb = -(-n // B)
+        self.rows = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.t = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.noise = torch.zeros(n, P, dtype=torch.float32, device=dev)
+        self.losses = torch.zeros(nb, dtype=torch.float32, device=dev)
+        if with_eps:
+            self.eps = torch.zeros(n, P, dtype=torch.float32, device=dev)
+            self.ctr = torch.zeros(nb, dtype=torch.int32, device=dev)
+
+
 class TrainPlan:
     """train_step for a fixed (B, L), captured ONCE as a graph
     (torch.cuda.CUDAGraph = hipGraph) and replayed per step: the draws
@@ -176,6 +261,7 @@ class TrainPlan:
         loss = plan.step(x0, cond)                # == train_step(...), bit for bit
         plan.x0.copy_(...); plan.cond.copy_(...)  # or fill the inputs in place
         plan.run(n)                               # n steps, no per-step host sync
+        losses = plan.run_epoch(data, order)      # a whole epoch of a DeviceDataset: one replay
 
     The graph addresses the parameters, their gradients and the Adam state:
     keep them (optimizer.step() / load_state_dict on the model copy in place;
@@ -230,6 +316,8 @@ class TrainPlan:
         self.freq = timestep_frequencies(_lib.HIDDEN, dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self._graphs = {}
+        self._ebufs = {}   # run_epoch: n_rows -> the buffers its graphs address
+        self.epoch_t = self.epoch_noise = None   # the last epoch's draws
         self._table_at(int(self._steps[0].item()))
         # warm-up outside any capture (module load, lazily created state): the
         # forward + backward on the zero inputs, into scratch gradient buffers --
@@ -390,6 +478,81 @@ class TrainPlan:
         for _ in range(n):
             self._replay(True)
 
+    @torch.no_grad()
+    def run_epoch(self, data, order, *, t=None, noise=None, drop_last: bool = False):
+        """One epoch (:308-320) over a device-resident dataset, as one graph
+        replay: batch i trains on data rows order[i*B : (i+1)*B], the last batch
+        with whatever is left (drop_last=True leaves it out, as DataLoader does).
+        Returns the per-batch losses as a device tensor (n_batches,); no host
+        sync (epoch_loss() turns them into the reference's epoch figure).
+
+        ``order``: any integer tensor of row indices into ``data`` -- not
+        necessarily a permutation, so a train split is ``train_idx[perm]``.  It
+        is range-checked before anything is launched (on the host for a CPU
+        tensor; one aminmax for a device tensor).  Every batch is bit for bit
+        the plan.step() on the gathered batch: same kernels, same draws (keyed
+        by seed, batch position and Adam step), same Adam bookkeeping.
+
+        t (n_rows,) / noise (n_rows, P), given together, replace the draws.
+        After the call the epoch's draws are in plan.epoch_t / plan.epoch_noise
+        (views of the graph's buffers: clone to keep them).  rng="torch" plans
+        draw the whole epoch's t, then its noise, from torch's generator before
+        the replay (not interleaved per batch as eager steps would).
+
+        One graph per (dataset, n_rows, draws or not) is captured on first use;
+        later epochs of the same length copy the new order in and replay."""
+        P = self.model.param_dim
+        _check_data(data, self.dev, self.L, P)
+        order, n = _epoch_order(order, len(data), self.B, drop_last)
+        nb = -(-n // self.B)
+        if nb >= self.TABLE:
+            raise RuntimeError(f"ertdiff: an epoch of {nb} batches does not fit the plan's table of "
+                               f"{self.TABLE} Adam steps")
+        draw = _check_draws(t, noise, n, P, self.alpha_bar.numel(), "TrainPlan.run_epoch")
+        bufs = self._ebufs.get(n)
+        if bufs is None:
+            bufs = self._ebufs[n] = _EpochBufs(n, self.B, P, self.dev)
+        self._sync_step()
+        if self.host_step + nb >= self.table_first + self.TABLE:
+            self._table_at(self.host_step)
+        dev_draw = draw and self.rng == "philox"
+        if draw and not dev_draw:
+            bufs.t.random_(0, self.T)
+            bufs.noise.normal_()
+        elif not draw:
+            bufs.t.copy_(t)
+            bufs.noise.copy_(noise)
+        bufs.rows.copy_(order)
+        key = ("epoch", n, dev_draw, data.x0.data_ptr(), data.cond.data_ptr(), len(data))
+        ent = self._graphs.get(key)
+        if ent is None:
+            w = self.model.weights_struct()
+            with torch.cuda.device(self.dev):
+                torch.cuda.synchronize(self.dev)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    _lib.check(_lib.lib().ertd_train_epoch_dev(
+                        ctypes.byref(w), data.x0.data_ptr(), data.cond.data_ptr(), len(data),
+                        bufs.rows.data_ptr(), n, bufs.t.data_ptr(), bufs.noise.data_ptr(),
+                        self.alpha_bar.data_ptr(), self.B, self.L, self.freq.data_ptr(),
+                        _lib.ptr_array(self.grads), _lib.ptr_array(self.exp_avg),
+                        _lib.ptr_array(self.exp_avg_sq), self.step_dev.data_ptr(),
+                        self.table.data_ptr(), self.table_first, self.TABLE, 1 if dev_draw else 0,
+                        self.T, self.seed, bufs.losses.data_ptr(), self.ws.data_ptr(),
+                        self.ws.numel(), _lib.stream_of(self.dev)), "train_epoch_dev")
+            ent = self._graphs[key] = (g, data)   # the graph addresses the dataset: keep it
+        with torch.cuda.device(self.dev):
+            ent[0].replay()
+        self.host_step += nb
+        self._step_base.add_(float(nb))
+        for p, gr in zip(self.params, self.grads):
+            if p.grad is not gr:
+                p.grad = gr
+        self.model._packed_key = None
+        increment_version(self.params)
+        self.epoch_t, self.epoch_noise = bufs.t, bufs.noise
+        return bufs.losses.clone()
+
 
 @torch.no_grad()
 def validation_loss(model, x0, cond, T, alpha_bar, *, t=None, noise=None) -> float:
@@ -404,3 +567,159 @@ def validation_loss(model, x0, cond, T, alpha_bar, *, t=None, noise=None) -> flo
     x_noisy = q_sample(x0, t, noise, alpha_bar)
     pred = model(x_noisy, t, cond)
     return F.mse_loss(pred, noise).item()
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def _validation_seed(seed: int) -> int:
+    """The Philox key of the validation draws: one splitmix64 round of ``seed``,
+    never equal to ``seed`` itself (the key of a TrainPlan on the same seed)."""
+    z = (int(seed) + 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    z ^= z >> 31
+    return z if z != (int(seed) & _MASK64) else z ^ 1
+
+
+class ValidationPlan:
+    """The validation pass (:325-338) over rows of a DeviceDataset as one graph
+    replay: per batch the train forward (the batch read through the row index),
+    eps and the batch's MSELoss; no backward -- parameters, gradients and Adam
+    state are not written.
+
+        val = ValidationPlan(model, B, L, T, alpha_bar, seed=seed)
+        losses = val.run(data, val_idx)            # device (n_batches,), no host sync
+        val.eps, val.t, val.noise                  # the call's predictions and draws
+
+    t ~ U{0..T-1} and noise ~ N(0, 1) are drawn in the head kernel, Philox keyed
+    (validation seed, batch position, counter); the plan holds the counter and
+    advances it by n_batches per call, so no two batches of any two calls share
+    a key, and the validation seed is derived from ``seed`` so that a TrainPlan
+    on the same ``seed`` draws a different stream.  The graph addresses the
+    parameters: keep them (in-place updates are followed)."""
+
+    def __init__(self, model, B: int, L: int, T: int, alpha_bar, seed=None):
+        model._check_supported()
+        self.model, self.T = model, int(T)
+        self.params = model._params()
+        dev = _lib.require_device(alpha_bar, self.params[0])
+        self.dev, self.B, self.L = dev, int(B), int(L)
+        if self.B < 1 or self.L < 1:
+            raise RuntimeError("ertdiff: ValidationPlan needs B >= 1 and L >= 1")
+        self.seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        self.val_seed = _validation_seed(self.seed)
+        self.alpha_bar = _lib.f32c(alpha_bar, "alpha_bar")
+        if self.alpha_bar.dim() != 1 or self.alpha_bar.numel() < self.T:
+            raise IndexError(f"ertdiff: alpha_bar has {self.alpha_bar.numel()} entries, "
+                             f"ValidationPlan needs at least T = {self.T}")
+        P = model.param_dim
+        self.ws = torch.empty(max(_lib.lib().ertd_workspace_bytes(self.B, self.L, P, 0, _lib.OP_TRAIN),
+                                  256), dtype=torch.uint8, device=dev)
+        self.freq = timestep_frequencies(_lib.HIDDEN, dev)
+        self.ctr = 0           # batches drawn so far (the Philox counter of the next batch)
+        self._bufs, self._graphs = {}, {}
+        self.eps = self.t = self.noise = None
+
+    def _call(self, data, bufs, n: int, draw: bool):
+        w = self.model.weights_struct()
+        _lib.check(_lib.lib().ertd_validation_epoch_dev(
+            ctypes.byref(w), data.x0.data_ptr(), data.cond.data_ptr(), len(data),
+            bufs.rows.data_ptr(), n, bufs.t.data_ptr(), bufs.noise.data_ptr(),
+            self.alpha_bar.data_ptr(), self.B, self.L, self.freq.data_ptr(), bufs.ctr.data_ptr(),
+            1 if draw else 0, self.T, self.val_seed, bufs.eps.data_ptr(), bufs.losses.data_ptr(),
+            self.ws.data_ptr(), self.ws.numel(), _lib.stream_of(self.dev)), "validation_epoch_dev")
+
+    @torch.no_grad()
+    def run(self, data, rows, *, t=None, noise=None):
+        """Per-batch validation losses (device, (n_batches,)) over data rows
+        ``rows`` in the given order, the last batch partial; checks as
+        TrainPlan.run_epoch.  t (n_rows,) / noise (n_rows, P) replace the draws."""
+        P = self.model.param_dim
+        _check_data(data, self.dev, self.L, P)
+        rows, n = _epoch_order(rows, len(data), self.B, False)
+        nb = -(-n // self.B)
+        draw = _check_draws(t, noise, n, P, self.alpha_bar.numel(), "ValidationPlan.run")
+        bufs = self._bufs.get(n)
+        if bufs is None:
+            bufs = self._bufs[n] = _EpochBufs(n, self.B, P, self.dev, with_eps=True)
+        if not draw:
+            bufs.t.copy_(t)
+            bufs.noise.copy_(noise)
+        bufs.rows.copy_(rows)
+        c0 = self.ctr % (1 << 30)   # int32 on the device
+        bufs.ctr.copy_(torch.arange(c0, c0 + nb, dtype=torch.int32, device=self.dev))
+        key = (n, draw, data.x0.data_ptr(), data.cond.data_ptr(), len(data))
+        ent = self._graphs.get(key)
+        if ent is None:
+            with torch.cuda.device(self.dev):
+                self._call(data, bufs, n, draw)   # once outside any capture: module load
+                torch.cuda.synchronize(self.dev)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    self._call(data, bufs, n, draw)
+            ent = self._graphs[key] = (g, data)
+        with torch.cuda.device(self.dev):
+            ent[0].replay()
+        self.ctr += nb
+        self.eps, self.t, self.noise = bufs.eps, bufs.t, bufs.noise
+        return bufs.losses.clone()
+
+
+def _weighted_mean(vals, n_rows: int, B: int) -> float:
+    sizes = batch_sizes(n_rows, B)
+    if len(vals) != len(sizes):
+        raise RuntimeError(f"ertdiff: {len(vals)} losses for {len(sizes)} batches of {n_rows} rows")
+    total = 0.0
+    for v, b in zip(vals, sizes):
+        total += v * b      # running_loss += loss.item() * B (:320)
+    return total / n_rows   # / len(dataset) (:322)
+
+
+def epoch_loss(losses, n_rows: int, B: int) -> float:
+    """The reference's epoch figure (:320-322, :336-338) from per-batch losses:
+    sum_i loss_i * B_i / n_rows in Python floats; one device-to-host copy."""
+    return _weighted_mean(losses.tolist(), n_rows, B)
+
+
+def fit(model, optimizer, data, train_idx, val_idx, T, alpha_bar, *, num_epochs: int,
+        batch_size: int = 32, checkpoint_path=None, generator=None, seed=None):
+    """The reference's training loop (:305-356) on a DeviceDataset: per epoch a
+    shuffled TrainPlan.run_epoch over train_idx, a ValidationPlan.run over
+    val_idx (unshuffled), one host read of both loss vectors, and on a better
+    validation loss the reference's checkpoint dict (save_checkpoint, epoch + 1)
+    at checkpoint_path.  Returns {"train_history", "val_history",
+    "best_val_loss", "best_epoch"} (best_epoch 1-based as in the checkpoint, 0
+    if no epoch ran).
+
+    The shuffle is train_idx[torch.randperm(n, generator=generator)] and t /
+    noise are the plans' Philox draws from ``seed``: this reproduces neither
+    DataLoader's sampler seeding nor the reference's mt19937 torch.randint /
+    torch.randn_like draws, so loss curves match the reference statistically,
+    not number for number."""
+    from .data import save_checkpoint
+    train_idx = torch.as_tensor(train_idx)
+    val_idx = torch.as_tensor(val_idx)
+    L = data.cond.shape[2]
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    plan = TrainPlan(model, optimizer, batch_size, L, T, alpha_bar, seed=seed)
+    val = ValidationPlan(model, batch_size, L, T, alpha_bar, seed=seed)
+    n_tr, n_va = train_idx.numel(), val_idx.numel()
+    train_history, val_history = [], []
+    best_val_loss, best_epoch = float("inf"), 0
+    gdev = generator.device if generator is not None else "cpu"
+    for epoch in range(int(num_epochs)):
+        perm = torch.randperm(n_tr, generator=generator, device=gdev)
+        tl = plan.run_epoch(data, train_idx[perm.to(train_idx.device)])
+        vl = val.run(data, val_idx)
+        both = torch.cat([tl, vl]).tolist()
+        train_history.append(_weighted_mean(both[:tl.numel()], n_tr, batch_size))
+        val_history.append(_weighted_mean(both[tl.numel():], n_va, batch_size))
+        if val_history[-1] < best_val_loss:
+            best_val_loss, best_epoch = val_history[-1], epoch + 1
+            if checkpoint_path is not None:
+                save_checkpoint(checkpoint_path, model, optimizer, epoch + 1, best_val_loss,
+                                train_history, val_history, model.param_dim)
+    return {"train_history": train_history, "val_history": val_history,
+            "best_val_loss": best_val_loss, "best_epoch": best_epoch}

@@ -285,6 +285,50 @@ int ertd_train_steps_dev(const ertd_weights* w, const float* x0, int64_t* t, flo
                          int draw, int T, uint64_t seed, int nsteps, float* loss_out, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* One training epoch (:309-320 for every batch of the loader) from a dataset
+ * resident on the device: x0_all (n_data,P), cond_all (n_data,14,L), and
+ * rows (n_rows) int32 row indices into them -- the epoch's order; any indices
+ * in [0, n_data), not necessarily a permutation.  The device cannot report a
+ * bad index: THE CALLER CHECKS 0 <= rows[i] < n_data (ertdiff.TrainPlan.run_epoch
+ * does).  Batch i takes rows[i*B .. min((i+1)*B, n_rows)); the last batch may
+ * be partial and runs as a step of its own, smaller B (mean over B_last * P).
+ * Each batch is one ertd_train_step_dev step -- the same four launches, the
+ * kernels reading member b's x0 / cond through rows[i*B + b] -- with batch i's
+ * t, noise and loss at t_all + i*B, noise_all + i*B*P and losses + i, so an
+ * epoch step is bit for bit the step on the gathered batch, and a replay of a
+ * captured graph of this call reads whatever order then sits in rows.
+ * draw = 1: every step draws its t / noise (Philox keyed (seed, batch
+ * position b, Adam step)) into its slice, so the epoch's draws are kept;
+ * draw = 0: the slices are inputs.  losses: (ceil(n_rows / B)).  ws: the
+ * ertd_workspace_bytes(B, L, P, 0, ERTD_OP_TRAIN) workspace.  Never allocates
+ * or syncs.  step_dev / adam_table as for ertd_train_step_dev, including the
+ * caveat: a step outside [table_first, table_first + table_len) is CLAMPED to
+ * the nearest entry, so the table must cover all ceil(n_rows / B) steps.
+ * ERTD_EINVAL for n_rows < 1, B < 1 or n_data < 1.                          */
+int ertd_train_epoch_dev(const ertd_weights* w, const float* x0_all, const float* cond_all,
+                         long long n_data, const int32_t* rows, int n_rows, int64_t* t_all,
+                         float* noise_all, const float* alpha_bar, int B, int L, const float* freq,
+                         float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                         int* step_dev, const float* adam_table, int table_first, int table_len,
+                         int draw, int T, uint64_t seed, float* losses, void* ws, size_t ws_bytes,
+                         void* stream);
+
+/* One validation epoch (:327-338) over rows of the same resident dataset:
+ * forward only -- no parameter, gradient or Adam state is written.  Per batch
+ * i: eps = model(q_sample(x0, t, noise), t, cond) into eps_all + i*B*P and
+ * losses[i] = MSELoss(mean)(eps, noise), summed in the train step's order.
+ * draw = 1: the batch draws t / noise keyed (seed, batch position b, ctr[i]);
+ * ctr (ceil(n_rows / B)) int32 on the device, filled by the caller with
+ * values that differ for every batch and every call.  draw = 0: t_all /
+ * noise_all are inputs (ctr may be NULL).  Same rows contract, workspace and
+ * capture rules as ertd_train_epoch_dev.                                     */
+int ertd_validation_epoch_dev(const ertd_weights* w, const float* x0_all, const float* cond_all,
+                              long long n_data, const int32_t* rows, int n_rows, int64_t* t_all,
+                              float* noise_all, const float* alpha_bar, int B, int L,
+                              const float* freq, const int* ctr, int draw, int T, uint64_t seed,
+                              float* eps_all, float* losses, void* ws, size_t ws_bytes,
+                              void* stream);
+
 /* The condition encoder's conv backward alone (the Conv1d part of
  * loss.backward(), :317), re-run on the state the last ertd_train_step /
  * ertd_train_step_dev / ertd_train_backward left in ws (same B, L, cond): it
