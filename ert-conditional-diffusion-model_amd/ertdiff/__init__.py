@@ -19,6 +19,7 @@ from .postproc import compact, postprocess, sample_realisations
 from .unet import ConditionalUNet, UNetSamplerPlan, sample_unet
 from .unet_train import UNetTrainPlan, unet_train_backward, unet_train_forward, unet_train_step
 from .kde import ensemble_mode, kde_mode, mode_kde_calculation
+from .prep import DeviceMinMaxScaler, prepare_dataset, split_indices
 from .stats import (WSSE_metric, accuracy_score, avg_prop_indicator_function, coverage_counts,
                     coverage_curve, coverage_from_counts, ensemble_moments, ensemble_percentile,
                     ensemble_summary, goodness_score, interval_fractions, mse,
@@ -39,4 +40,5 @@ __all__ = [
     "avg_prop_indicator_function", "accuracy_score", "preccision_score", "goodness_score",
     "uncertainty_metrics", "sort_rows", "wasserstein", "wasserstein_distance", "mse",
     "DeviceDataset", "ValidationPlan", "epoch_loss", "fit",
+    "DeviceMinMaxScaler", "prepare_dataset", "split_indices",
 ]

@@ -191,6 +191,13 @@ SIGNATURES = {
     "ertd_rows_sort": (_I, [_VP, _I, _I, _LL, _LL, _VP, _VP, _SZ, _VP]),
     "ertd_wasserstein_ws_bytes": (_SZ, [_I, _I, _LL, _LL]),
     "ertd_wasserstein": (_I, [_VP, _I, _I, _LL, _LL, _VP, _LL, _VP, _VP, _SZ, _VP]),
+    "ertd_minmax_ws_bytes": (_SZ, [_LL, _LL]),
+    "ertd_minmax_partial_fit": (_I, [_VP, _LL, _LL, _LL, _VP, _VP, _I, _VP, _SZ, _VP]),
+    "ertd_minmax_finalize": (_I, [_VP, _VP, _LL, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _VP]),
+    "ertd_minmax_transform": (_I, [_VP, _LL, _LL, _LL, _VP, _VP, _VP, _LL, _VP]),
+    "ertd_minmax_inverse": (_I, [_VP, _I, _LL, _LL, _LL, _VP, _VP, _VP, _LL, _VP]),
+    "ertd_minmax_cond": (_I, [_VP, _LL, _I, _I, _VP, _VP, _VP, _VP]),
+    "ertd_minmax_cond_inverse": (_I, [_VP, _LL, _I, _I, _VP, _VP, _VP, _VP]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -765,6 +765,63 @@ int ertd_wasserstein(const void* u, int dtype, int n, long long Mu, long long ld
                      const void* v, long long Mv, double* out,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- MinMax scaling and the training set on the device (csrc/dataprep.hip) ----
+ * Replaces the host sklearn / numpy of the reference's scaling cell
+ * ERT_Conditional_Diffusion.py:230-269 (MinMaxScaler.fit_transform of the
+ * (5076, 65702) float64 ERT array and of the (5076, 29) parameters, then
+ * DiffusionDataset's transpose :72 and .float()) and of :417-419
+ * (ert_scaler.inverse_transform of float32 conditions after a swapaxes).
+ * Every float64 operation is one separately rounded IEEE operation in
+ * sklearn 1.7's order, so the results equal sklearn's bit for bit.  All
+ * arrays are on the device; X is row-major with a row pitch of ldx values.
+ * No allocation, no host synchronisation.                                   */
+/* Workspace of ertd_minmax_partial_fit: the per-slab column minima and maxima
+ * (0 for arguments the call would reject).                                  */
+size_t ertd_minmax_ws_bytes(long long n, long long F);
+/* data_min[f] = np.nanmin(X[:, f]), data_max[f] = np.nanmax(X[:, f]) over the
+ * n rows: a NaN is skipped, an all-NaN column yields NaN.  accumulate != 0:
+ * the result is then combined with the values already in data_min /
+ * data_max by np.minimum / np.maximum (which propagate a NaN) -- one
+ * MinMaxScaler.partial_fit call after the first.  16-byte loads when F and
+ * ldx are even and X is 16-byte aligned, 8-byte loads otherwise.            */
+int ertd_minmax_partial_fit(const double* X, long long n, long long F, long long ldx,
+                            double* data_min, double* data_max, int accumulate, void* ws,
+                            size_t ws_bytes, void* stream);
+/* The fitted vectors for feature_range (fr0, fr1), each (F) float64:
+ *   range  = data_max - data_min                      (data_range_; optional)
+ *   scale  = (fr1 - fr0) / (range < 10 DBL_EPSILON ? 1 : range)   (scale_)
+ *   min_   = fr0 - data_min * scale                   (min_)
+ * A NaN range stays NaN (the comparison is false), as in sklearn.           */
+int ertd_minmax_finalize(const double* data_min, const double* data_max, long long F, double fr0,
+                         double fr1, double* scale, double* min_, double* range, void* stream);
+/* MinMaxScaler.transform in float64: out[i, f] = X[i, f] * scale[f] + min_[f],
+ * the product and the sum each rounded.  out (row pitch ldo) may be X.      */
+int ertd_minmax_transform(const double* X, long long n, long long F, long long ldx,
+                          const double* scale, const double* min_, double* out, long long ldo,
+                          void* stream);
+/* MinMaxScaler.inverse_transform in X's dtype (ERTD_F32 / ERTD_F64):
+ * t = X[i, f] - min_[f]; out[i, f] = t / scale[f].  Both operations are
+ * float64; for a float32 array t and the quotient are each rounded to
+ * float32 (sklearn applies -= and /= in place to the float32 array).  out
+ * (row pitch ldo, X's dtype) may be X.                                      */
+int ertd_minmax_inverse(const void* X, int dtype, long long n, long long F, long long ldx,
+                        const double* scale, const double* min_, void* out, long long ldo,
+                        void* stream);
+/* Scale, transpose and narrow in one pass (:259-261, :72, .float()):
+ * X (n, L, C) float64 contiguous, scale / min_ (L * C) ->
+ *   cond[i, c, l] = (float)(X[i, l, c] * scale[l C + c] + min_[l C + c])
+ * cond (n, C, L) float32 contiguous: the product and the sum are rounded to
+ * float64, then one round-to-nearest-even narrowing.  1 <= C <= 16; C = 14
+ * with a 16-byte aligned X is the tuned path.  To fill rows
+ * r0.. of a larger (N, C, L) buffer pass cond + r0 * C * L.                 */
+int ertd_minmax_cond(const double* X, long long n, int L, int C, const double* scale,
+                     const double* min_, float* cond, void* stream);
+/* The way back (:417-419): cond (n, C, L) float32 -> out (n, L, C) float32,
+ *   t = (float)(cond[i, c, l] - min_[l C + c]); out[i, l, c] = (float)(t / scale[l C + c])
+ * with float64 operations, as ertd_minmax_inverse does for a float32 array. */
+int ertd_minmax_cond_inverse(const float* cond, long long n, int L, int C, const double* scale,
+                             const double* min_, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
