@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "ertd_common.h"
 
@@ -205,6 +206,33 @@ int enqueue_sample(const ertd_weights* w, const float* packed, const float* cond
 
 }  // namespace
 
+namespace ertd {
+
+// The solver tables live on the device; they are read back once (K ints and
+// 6K floats, a blocking copy ordered after `s`) so that a table the kernels
+// would index out of bounds with is refused before anything is enqueued:
+// timesteps strictly descending and >= 0, c_k == 0 unless a D_prev buffer is
+// given, c_0 == 0 (D_prev is zero before the first step), and with an
+// injected (K, B, P) noise buffer s_{K-1} == 0 (step k reads row k + 1).
+int solver_tables_ok(const int32_t* timesteps, const float* coef, int K, bool have_d_prev,
+                     bool have_noise, hipStream_t s) {
+  if (K < 1 || K > (1 << 20)) return ERTD_EINVAL;
+  std::vector<int32_t> ts((size_t)K);
+  std::vector<float> cf((size_t)K * 6);
+  ERTD_TRY(hipMemcpyAsync(ts.data(), timesteps, ts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  ERTD_TRY(hipMemcpyAsync(cf.data(), coef, cf.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  ERTD_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < K; ++k) {
+    if (ts[k] < 0 || (k > 0 && ts[k] >= ts[k - 1])) return ERTD_EINVAL;
+    const float c = cf[(size_t)k * 6 + 4];
+    if (c != 0.f && (!have_d_prev || k == 0)) return ERTD_EINVAL;
+  }
+  if (have_noise && cf[(size_t)(K - 1) * 6 + 5] != 0.f) return ERTD_EINVAL;
+  return ERTD_OK;
+}
+
+}  // namespace ertd
+
 struct ertd_plan {
   hipStream_t stream = nullptr;
   hipGraph_t graph = nullptr;
@@ -335,6 +363,40 @@ int ertd_sample_status(const void* ws, int B, int L, int num_steps, int* status,
   ERTD_TRY(hipStreamSynchronize((hipStream_t)stream));
   *status = (int)v;
   return v == 0 ? ERTD_OK : ERTD_ETIMEOUT;
+}
+
+int ertd_sample_solver(const ertd_weights* w, const float* packed, const float* cond,
+                       long long cond_stride, int B, int L, int K, int k_first, int n_run,
+                       const int32_t* timesteps, const float* coef, float clip, const float* freq,
+                       const float* noise, uint64_t seed, uint32_t member_offset, int mode,
+                       int precision, float* x_inout, float* d_prev_inout, void* ws,
+                       size_t ws_bytes, void* stream) {
+  if (!weights_ok(w) || !packed || !cond || !timesteps || !coef || !freq || !x_inout || !ws)
+    return ERTD_EINVAL;
+  // hoisted evaluation only: the faithful schedules would produce the same bits
+  if (mode != ERTD_MODE_HOISTED) return ERTD_EINVAL;
+  if (B < 1 || L < 1 || K < 1 || k_first < 0 || n_run < 1 || n_run > K - k_first || !(clip >= 0.f))
+    return ERTD_EINVAL;
+  if (precision != ERTD_PREC_FP32 && precision != ERTD_PREC_BF16) return ERTD_EINVAL;
+  if (cond_stride != 0 && cond_stride < (long long)CIN * L) return ERTD_EINVAL;
+  Ws W;
+  if (ws_layout(B, L, K, ERTD_OP_SAMPLE, ws, &W) > ws_bytes) return ERTD_ENOSPC;
+  hipStream_t s = (hipStream_t)stream;
+  const int r = solver_tables_ok(timesteps, coef, K, d_prev_inout != nullptr, noise != nullptr, s);
+  if (r != ERTD_OK) return r;
+  const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
+  ERTD_TRY(launch_encoder_strips(packed, w->enc0_b, w->enc2_b, cond, cond_stride, B, L, precision,
+                                 W.partial, s));
+  ERTD_TRY(launch_hoist_prep(*w, packed, W.partial, S, L2, B, W.U, W.cond_emb, s));
+  ERTD_TRY(launch_solver_time_table(*w, packed, freq, timesteps, k_first, n_run, W.V, s));
+  return rc(launch_solver_sampler(*w, packed, W.U, W.V, timesteps, coef, clip, noise, k_first, n_run,
+                                  seed, member_offset, B, x_inout, d_prev_inout, s));
+}
+
+int ertd_solver_update(float* x, const float* eps, float* d_prev, const float* coef_row, float clip,
+                       const float* z, int B, int P, void* stream) {
+  if (!x || !eps || !coef_row || B < 1 || P < 1 || !(clip >= 0.f)) return ERTD_EINVAL;
+  return rc(launch_solver_update(x, eps, d_prev, coef_row, clip, z, B, P, (hipStream_t)stream));
 }
 
 int ertd_philox_normal(uint64_t seed, uint32_t member_offset, int B, int P, int t, int tag,

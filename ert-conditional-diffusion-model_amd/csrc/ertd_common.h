@@ -251,6 +251,19 @@ hipError_t launch_hoisted_sampler(const ertd_weights& w, const float* packed, co
                                   int t_first, int n_run, uint64_t seed, uint32_t member_offset,
                                   int B, float* x, hipStream_t s, int ncond = 0, int id_period = 0,
                                   int u_rows = 0);
+// few-step solver sampler (head.hip): V row k = the time row of timesteps[k]
+hipError_t launch_solver_time_table(const ertd_weights& w, const float* packed, const float* freq,
+                                    const int* timesteps, int k_lo, int n, float* V, hipStream_t s);
+hipError_t launch_solver_sampler(const ertd_weights& w, const float* packed, const float* U,
+                                 const float* V, const int* timesteps, const float* coef, float clip,
+                                 const float* noise, int k_first, int n_run, uint64_t seed,
+                                 uint32_t member_offset, int B, float* x, float* d_prev,
+                                 hipStream_t s);
+hipError_t launch_solver_update(float* x, const float* eps, float* d_prev, const float* coef_row,
+                                float clip, const float* z, int B, int P, hipStream_t s);
+// capi.hip: host check of the device-resident solver tables (blocking read-back)
+int solver_tables_ok(const int32_t* timesteps, const float* coef, int K, bool have_d_prev,
+                     bool have_noise, hipStream_t s);
 hipError_t launch_timestep_embedding(const int64_t* t, int B, int dim, const float* freq,
                                      float* out, hipStream_t s);
 hipError_t launch_q_sample(const float* x0, const int64_t* t, const float* noise,

@@ -306,6 +306,95 @@ hipError_t launch_hoisted_sampler(const ertd_weights& w, const float* packed, co
   return hipGetLastError();
 }
 
+// ---- persistent few-step solver sampler -----------------------------------------------
+// The hoisted sampler's twin on a timestep subset: step k evaluates the model
+// at timesteps[k] and applies solver_update with row k of coef.  V holds one
+// time row per step (row k = time_row(timesteps[k]), the row the ancestral
+// sampler uses for that t).  x and D_prev live in registers over the steps.
+__global__ __launch_bounds__(256) void solver_time_table_kernel(
+    ertd_weights w, const float* __restrict__ packed, const float* __restrict__ freq,
+    const int* __restrict__ timesteps, int k_lo, float* __restrict__ V) {
+  __shared__ TimeScratch sc;
+  const int k = k_lo + (int)blockIdx.x;
+  time_row(sc, w, dense_ptrs(packed), freq, timesteps[k], V + (size_t)k * H, threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void solver_sampler_kernel(
+    ertd_weights w, const float* __restrict__ packed, const float* __restrict__ U,
+    const float* __restrict__ V, const int* __restrict__ timesteps, const float* __restrict__ coef,
+    float clip, const float* __restrict__ noise, int k_first, int n_run, uint64_t seed,
+    uint32_t member_offset, int B, float* __restrict__ x, float* __restrict__ d_prev) {
+  __shared__ float hbuf[4][H];
+  __shared__ float xbuf[4][PMAX];
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;  // whole wave exits together (no block barriers below)
+  const int P = w.param_dim;
+  StepRegs R;
+  load_step_regs(R, packed, w.mlp2_b, P, lane);
+  const float u_lo = U[(size_t)b * H + lane];
+  const float u_hi = U[(size_t)b * H + 64 + lane];
+  const int o = lane >> 1;
+  const uint32_t member = member_offset + (uint32_t)b;
+  float xv = o < P ? x[(size_t)b * P + o] : 0.f;
+  // D_prev is zero before the first step of a chain; a later segment reads
+  // what the previous one stored
+  float dp = (d_prev && k_first > 0 && o < P) ? d_prev[(size_t)b * P + o] : 0.f;
+  float xs[PMAX];
+  for (int k = k_first; k < k_first + n_run; ++k) {
+    broadcast_x(xs, xv, P, lane, xbuf[threadIdx.x >> 6]);
+    const int t = timesteps[k];
+    const SolverRow row = load_solver_row(coef, k);
+    const float w_lo = u_lo + V[(size_t)k * H + lane];
+    const float w_hi = u_hi + V[(size_t)k * H + 64 + lane];
+    const float z = (row.s != 0.f && o < P) ? solver_noise(noise, k, t, B, b, P, o, seed, member) : 0.f;
+    const RegSrc src{R, R.bo};
+    const float eps = step_eps(src, w_lo, w_hi, xs, P, lane, hbuf[threadIdx.x >> 6]);
+    xv = solver_update(xv, eps, dp, z, row, clip, dp);
+  }
+  if (!(lane & 1) && o < P) {
+    x[(size_t)b * P + o] = xv;
+    if (d_prev) d_prev[(size_t)b * P + o] = dp;
+  }
+}
+
+hipError_t launch_solver_time_table(const ertd_weights& w, const float* packed, const float* freq,
+                                    const int* timesteps, int k_lo, int n, float* V, hipStream_t s) {
+  solver_time_table_kernel<<<n, 256, 0, s>>>(w, packed, freq, timesteps, k_lo, V);
+  return hipGetLastError();
+}
+
+hipError_t launch_solver_sampler(const ertd_weights& w, const float* packed, const float* U,
+                                 const float* V, const int* timesteps, const float* coef, float clip,
+                                 const float* noise, int k_first, int n_run, uint64_t seed,
+                                 uint32_t member_offset, int B, float* x, float* d_prev,
+                                 hipStream_t s) {
+  solver_sampler_kernel<<<(B + 3) / 4, 256, 0, s>>>(w, packed, U, V, timesteps, coef, clip, noise,
+                                                     k_first, n_run, seed, member_offset, B, x, d_prev);
+  return hipGetLastError();
+}
+
+// The bare update on a (B, P) state: one coefficient row, an explicit z.
+__global__ void solver_update_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                     float* __restrict__ d_prev, const float* __restrict__ coef_row,
+                                     float clip, const float* __restrict__ z, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const SolverRow row = load_solver_row(coef_row, 0);
+  const float dp = (d_prev && row.c != 0.f) ? d_prev[i] : 0.f;
+  const float zv = (z && row.s != 0.f) ? z[i] : 0.f;
+  float d;
+  x[i] = solver_update(x[i], eps[i], dp, zv, row, clip, d);
+  if (d_prev) d_prev[i] = d;
+}
+
+hipError_t launch_solver_update(float* x, const float* eps, float* d_prev, const float* coef_row,
+                                float clip, const float* z, int B, int P, hipStream_t s) {
+  const size_t n = (size_t)B * P;
+  solver_update_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, eps, d_prev, coef_row, clip, z, n);
+  return hipGetLastError();
+}
+
 // ---- small API kernels -------------------------------------------------------------
 __global__ void timestep_embedding_kernel(const int64_t* __restrict__ t, int B, int dim,
                                           const float* __restrict__ freq, float* __restrict__ out) {

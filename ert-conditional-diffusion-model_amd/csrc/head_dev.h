@@ -233,6 +233,54 @@ __device__ __forceinline__ float ddpm_update(float xv, float eps, float c1, floa
   return add_noise ? t3 + sig * z : t3;
 }
 
+// One step of a few-step solver on a timestep subset (DDIM, DPM-Solver++(2M)):
+//   D = p*x + q*eps;  D = clamp(D, -clip, clip) if clip > 0
+//   x <- a*x + b*D [+ c*D_prev] [+ s*z];  D_prev <- D
+// row = {p, q, a, b, c, s} (ertdiff/schedule.py solver_tables).  Fixed order,
+// one fp32 rounding per line, no contraction:
+//   t1 = p*x;  t2 = q*eps;  D = t1 + t2;  (clamp: fminf(fmaxf(D, -clip), clip))
+//   r  = a*x;  t3 = b*D;    r = r + t3;
+//   c != 0:  t4 = c*D_prev;  r = r + t4
+//   s != 0:  t5 = s*z;       r = r + t5
+// A term whose coefficient is zero is skipped, not added as zero: the caller
+// neither reads D_prev when c == 0 nor reads or draws z when s == 0, and
+// passes 0 for them.  Returns the new x, the (clamped) D in d_out.
+struct SolverRow {
+  float p, q, a, b, c, s;
+};
+__device__ __forceinline__ SolverRow load_solver_row(const float* __restrict__ coef, int k) {
+  const float* r = coef + (size_t)k * 6;
+  return SolverRow{r[0], r[1], r[2], r[3], r[4], r[5]};
+}
+__device__ __forceinline__ float solver_update(float xv, float eps, float d_prev, float z,
+                                               const SolverRow& c, float clip, float& d_out) {
+  const float t1 = c.p * xv;
+  const float t2 = c.q * eps;
+  float D = t1 + t2;
+  if (clip > 0.f) D = fminf(fmaxf(D, -clip), clip);
+  float r = c.a * xv;
+  const float t3 = c.b * D;
+  r = r + t3;
+  if (c.c != 0.f) {
+    const float t4 = c.c * d_prev;
+    r = r + t4;
+  }
+  if (c.s != 0.f) {
+    const float t5 = c.s * z;
+    r = r + t5;
+  }
+  d_out = D;
+  return r;
+}
+// z of solver step k at timestep t: the ancestral sampler's Philox stream
+// (seed, member, t, tag 0), or row k+1 of an injected (K, B, P) buffer (row 0
+// is x_T).  Call only when the row's s != 0.
+__device__ __forceinline__ float solver_noise(const float* __restrict__ noise, int k, int t, int B,
+                                              int b, int P, int o, uint64_t seed, uint32_t member) {
+  if (noise) return noise[((size_t)(k + 1) * B + b) * P + o];
+  return philox_normal(seed, member, (uint32_t)t, 0u, o);
+}
+
 __device__ __forceinline__ float step_noise(const float* __restrict__ noise, int num_steps, int t,
                                             int B, int b, int P, int o, uint64_t seed,
                                             uint32_t member) {

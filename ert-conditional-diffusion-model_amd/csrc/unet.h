@@ -492,6 +492,27 @@ hipError_t launch_sum_pool2(const float* x, int B, int C, int H, float* out, int
                             hipStream_t s);
 hipError_t launch_set_word(int* w, int v, hipStream_t s);
 hipError_t launch_dec_word(int* w, hipStream_t s);
+// Few-step solver step (head_dev.h solver_update) on the (B, P) state.  The
+// step graph keeps two words: words[0] = the timestep of the current step (the
+// embedding reads it, as the ancestral sampler's counter), words[1] = the
+// step index k (the update reads row k of coef and, injected, noise row k+1).
+struct SolverUpdateArgs {
+  float* x;             // (B, P) in/out
+  const float* eps;     // (B, P)
+  float* d_prev;        // (B, P) in/out
+  const float* coef;    // (K, 6)
+  const float* noise;   // injected (K, B, P) or null -> Philox
+  const int* words;     // {timestep, k}
+  int K;                // rows of coef: a step with k outside [0, K) does nothing
+  float clip;
+  uint64_t seed; uint32_t member_offset;
+  int P;
+};
+hipError_t launch_unet_solver_update(const SolverUpdateArgs& a, int B, hipStream_t s);
+// words := {timesteps[k], k}
+hipError_t launch_solver_set_words(int* words, const int* timesteps, int k, hipStream_t s);
+// k := k + 1, timestep := timesteps[k] (0 past the last of the K steps)
+hipError_t launch_solver_next_words(int* words, const int* timesteps, int K, hipStream_t s);
 
 }  // namespace unet
 }  // namespace ertd

@@ -810,11 +810,73 @@ struct SampleCall {
   }
 };
 
+// One few-step solver call on a timestep subset: the same head and step as
+// SampleCall, with two words in the counter slot -- {timestep of the current
+// step, step index k} -- the solver update (head_dev.h solver_update) in
+// place of the DDPM update, and a word kernel that advances both words from
+// the device timesteps table.
+struct SolverCall {
+  const ertd_unet_config* c;
+  const float* packed; const float* cond; long long cond_stride; int L; int B;
+  int K; int k_first; int n_run;
+  const int32_t* timesteps; const float* coef; float clip; const float* noise;
+  uint64_t seed; uint32_t member_offset; float* x; float* d_prev; void* ws; size_t ws_bytes;
+
+  // the tables are read back (blocking) on `s`: call it outside a capture
+  int check(hipStream_t s) const {
+    if (!cfg_ok(c) || !packed || !cond || !timesteps || !coef || !x || !d_prev || !ws || B < 1 ||
+        L < 1 || K < 1 || k_first < 0 || n_run < 0 || n_run > K - k_first || !(clip >= 0.f))
+      return ERTD_EINVAL;
+    const Layout Lo = layout_with_freq(c);
+    if (ws_bytes_for(c, Lo, B, L) > ws_bytes) return ERTD_ENOSPC;
+    return solver_tables_ok(timesteps, coef, K, true, noise != nullptr, s);
+  }
+  int head(hipStream_t s) const {
+    const Layout Lo = layout_with_freq(c);
+    Walk w{c, &Lo, packed, (char*)ws, 0, B, s, false};
+    w.cap = ws_bytes;
+    const Fixed f = fixed(w, L);
+    const int r = prologue(w, f, cond, cond_stride, L);
+    if (r != ERTD_OK) return r;
+    w.chk(launch_solver_set_words(f.tdev, timesteps, k_first, s));
+    return rcode(w.err);
+  }
+  int step(hipStream_t s, hipStream_t s2 = nullptr, hipEvent_t evf = nullptr,
+           hipEvent_t evj = nullptr, hipEvent_t eve = nullptr, bool skip_side = true) const {
+    const Layout Lo = layout_with_freq(c);
+    Walk w{c, &Lo, packed, (char*)ws, 0, B, s, false};
+    w.cap = ws_bytes;
+    w.s2 = skip_side ? s2 : nullptr;
+    w.evf = evf;
+    w.evj = evj;
+    const Fixed f = fixed(w, L);
+    const int P = c->image * c->image;
+    if (s2 && eve) {
+      w.chk(hipEventRecord(evf, s));
+      w.chk(hipStreamWaitEvent(s2, evf, 0));
+      w.s = s2;
+      embed(w, f, nullptr);
+      w.s = s;
+      w.chk(hipEventRecord(eve, s2));
+      w.emb_join = eve;
+    } else {
+      embed(w, f, nullptr);
+    }
+    w.unet(x, f.ebias, f.eps);
+    SolverUpdateArgs u{x, f.eps, d_prev, coef, noise, f.tdev, K, clip, seed, member_offset, P};
+    w.chk(launch_unet_solver_update(u, B, s));
+    w.chk(launch_solver_next_words(f.tdev, timesteps, K, s));
+    return rcode(w.err);
+  }
+};
+
 }  // namespace
 
 struct ertd_unet_plan {
   ertd_unet_config cfg{};
   SampleCall call{};
+  SolverCall scall{};                    // a solver plan's call (ertd_unet_sample_solver_plan_create)
+  int n_run = 0;
   hipStream_t stream = nullptr;
   hipStream_t side = nullptr;            // skip-conv branch of the step graph
   hipEvent_t evf = nullptr, evj = nullptr, eve = nullptr;
@@ -827,6 +889,57 @@ struct ertd_unet_plan {
   int multi = 0;
   bool skip_side = false;                // the skip convs on the side stream too
 };
+
+// The graphs of a checked plan: head, one step, and MULTI consecutive steps.
+// `call` is the plan's own SampleCall or SolverCall (same head / step shape).
+template <class Call>
+static int capture_unet_plan(ertd_unet_plan* p, const Call& call, ertd_unet_plan** plan) {
+  int r = ERTD_OK;
+  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+  // The forked skip-conv branch pays only where the convs leave CUs free: the
+  // fp32 Winograd kernel is persistent (one workgroup on every CU), so the side
+  // branch's convs queue behind it and slow it (U2 B=64: 154.9 steps/s single
+  // chain vs 152.6 forked); the bf16 path keeps it (U3 B=256: 94.0 vs 93.1).
+  // ERTD_UNET_SIDE=0/1 overrides (A/B).
+  const int sv = ERTD_KNOB("UNET_SIDE", -1);
+  const bool side = sv >= 0 ? sv != 0 : bf_prec(p->cfg.precision);
+  // the embedding branch alone beside conv_in and the first GroupNorm
+  // (ERTD_UNET_SIDE_EMB=1, A/B): slower, U2 B=64 246.1 vs 249.7 steps/s -- the
+  // cross-queue event waits of a forked graph cost more than the overlap
+  const bool side_emb = ERTD_KNOB("UNET_SIDE_EMB", 0) != 0;
+  p->skip_side = side;
+  if (e == hipSuccess && (side || side_emb)) {
+    e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->evf, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->evj, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->eve, hipEventDisableTiming);
+  }
+  const int multi = ERTD_KNOB("UNET_MULTI", 8);   // U2 B=64: 248.6 (1) vs 249.0 (4) vs 249.4 (8) steps/s
+  const int ngraphs = multi > 1 && p->n_run >= 2 * multi ? 3 : 2;
+  for (int k = 0; e == hipSuccess && k < ngraphs; ++k) {
+    e = hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) break;
+    if (k == 0) {
+      r = call.head(p->stream);
+    } else {
+      for (int i = 0; r == ERTD_OK && i < (k == 1 ? 1 : multi); ++i)
+        r = call.step(p->stream, p->side, p->evf, p->evj, p->eve, p->skip_side);
+    }
+    hipGraph_t g = nullptr;
+    e = hipStreamEndCapture(p->stream, &g);
+    (k == 0 ? p->g_head : k == 1 ? p->g_step : p->g_multi) = g;
+    if (r != ERTD_OK) break;
+    if (e == hipSuccess)
+      e = hipGraphInstantiate(k == 0 ? &p->x_head : k == 1 ? &p->x_step : &p->x_multi, g, nullptr, nullptr, 0);
+    if (k == 2 && e == hipSuccess) p->multi = multi;
+  }
+  if (r != ERTD_OK || e != hipSuccess) {
+    ertd_unet_plan_destroy(p);
+    return r != ERTD_OK ? r : (int)e;
+  }
+  *plan = p;
+  return ERTD_OK;
+}
 
 extern "C" {
 
@@ -1357,59 +1470,61 @@ int ertd_unet_sample_plan_create(const ertd_unet_config* c, const float* packed,
                        sigma, noise, seed, member_offset, x_inout, ws, ws_bytes};
   p->cfg = *c;
   p->call.c = &p->cfg;
+  p->n_run = n_run;
   int r = p->call.check();
   if (r != ERTD_OK) {
     delete p;
     return r;
   }
-  hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-  // The forked skip-conv branch pays only where the convs leave CUs free: the
-  // fp32 Winograd kernel is persistent (one workgroup on every CU), so the side
-  // branch's convs queue behind it and slow it (U2 B=64: 154.9 steps/s single
-  // chain vs 152.6 forked); the bf16 path keeps it (U3 B=256: 94.0 vs 93.1).
-  // ERTD_UNET_SIDE=0/1 overrides (A/B).
-  const int sv = ERTD_KNOB("UNET_SIDE", -1);
-  const bool side = sv >= 0 ? sv != 0 : bf_prec(c->precision);
-  // the embedding branch alone beside conv_in and the first GroupNorm
-  // (ERTD_UNET_SIDE_EMB=1, A/B): slower, U2 B=64 246.1 vs 249.7 steps/s -- the
-  // cross-queue event waits of a forked graph cost more than the overlap
-  const bool side_emb = ERTD_KNOB("UNET_SIDE_EMB", 0) != 0;
-  p->skip_side = side;
-  if (e == hipSuccess && (side || side_emb)) {
-    e = hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->evf, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->evj, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->eve, hipEventDisableTiming);
-  }
-  const int multi = ERTD_KNOB("UNET_MULTI", 8);   // U2 B=64: 248.6 (1) vs 249.0 (4) vs 249.4 (8) steps/s
-  const int ngraphs = multi > 1 && n_run >= 2 * multi ? 3 : 2;
-  for (int k = 0; e == hipSuccess && k < ngraphs; ++k) {
-    e = hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) break;
-    if (k == 0) {
-      r = p->call.head(p->stream);
-    } else {
-      for (int i = 0; r == ERTD_OK && i < (k == 1 ? 1 : multi); ++i)
-        r = p->call.step(p->stream, p->side, p->evf, p->evj, p->eve, p->skip_side);
-    }
-    hipGraph_t g = nullptr;
-    e = hipStreamEndCapture(p->stream, &g);
-    (k == 0 ? p->g_head : k == 1 ? p->g_step : p->g_multi) = g;
-    if (r != ERTD_OK) break;
-    if (e == hipSuccess)
-      e = hipGraphInstantiate(k == 0 ? &p->x_head : k == 1 ? &p->x_step : &p->x_multi, g, nullptr, nullptr, 0);
-    if (k == 2 && e == hipSuccess) p->multi = multi;
-  }
-  if (r != ERTD_OK || e != hipSuccess) {
-    ertd_unet_plan_destroy(p);
-    return r != ERTD_OK ? r : (int)e;
-  }
-  *plan = p;
+  return capture_unet_plan(p, p->call, plan);
+}
+
+int ertd_unet_sample_solver(const ertd_unet_config* c, const float* packed, const float* cond,
+                            long long cond_stride, int L, int B, int K, int k_first, int n_run,
+                            const int32_t* timesteps, const float* coef, float clip,
+                            const float* noise, uint64_t seed, uint32_t member_offset,
+                            float* x_inout, float* d_prev_inout, void* ws, size_t ws_bytes,
+                            void* stream) {
+  SolverCall sc{c, packed, cond, cond_stride, L, B, K, k_first, n_run, timesteps, coef, clip,
+                noise, seed, member_offset, x_inout, d_prev_inout, ws, ws_bytes};
+  hipStream_t s = (hipStream_t)stream;
+  int r = sc.check(s);
+  if (r != ERTD_OK) return r;
+  if ((r = sc.head(s)) != ERTD_OK) return r;
+  for (int i = 0; i < n_run; ++i)
+    if ((r = sc.step(s)) != ERTD_OK) return r;
   return ERTD_OK;
 }
 
+int ertd_unet_sample_solver_plan_create(const ertd_unet_config* c, const float* packed,
+                                        const float* cond, long long cond_stride, int L, int B,
+                                        int K, int k_first, int n_run, const int32_t* timesteps,
+                                        const float* coef, float clip, const float* noise,
+                                        uint64_t seed, uint32_t member_offset, float* x_inout,
+                                        float* d_prev_inout, void* ws, size_t ws_bytes,
+                                        void* stream, ertd_unet_plan** plan) {
+  if (!plan) return ERTD_EINVAL;
+  *plan = nullptr;
+  if (!c) return ERTD_EINVAL;
+  ertd_unet_plan* p = new (std::nothrow) ertd_unet_plan();
+  if (!p) return ERTD_EINVAL;
+  p->scall = SolverCall{c, packed, cond, cond_stride, L, B, K, k_first, n_run, timesteps, coef,
+                        clip, noise, seed, member_offset, x_inout, d_prev_inout, ws, ws_bytes};
+  p->cfg = *c;
+  p->scall.c = &p->cfg;
+  p->n_run = n_run;
+  // the tables are checked here, once, on the caller's stream (a blocking
+  // read-back); the captured graphs then read them on the device every replay
+  const int r = p->scall.check((hipStream_t)stream);
+  if (r != ERTD_OK) {
+    delete p;
+    return r;
+  }
+  return capture_unet_plan(p, p->scall, plan);
+}
+
 int ertd_unet_plan_launch_steps(ertd_unet_plan* p, int n_steps, void* stream) {
-  if (!p || !p->x_head || !p->x_step || n_steps < 0 || n_steps > p->call.n_run) return ERTD_EINVAL;
+  if (!p || !p->x_head || !p->x_step || n_steps < 0 || n_steps > p->n_run) return ERTD_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipGraphLaunch(p->x_head, s);
   int i = 0;
@@ -1421,7 +1536,7 @@ int ertd_unet_plan_launch_steps(ertd_unet_plan* p, int n_steps, void* stream) {
 
 int ertd_unet_plan_launch(ertd_unet_plan* p, void* stream) {
   if (!p) return ERTD_EINVAL;
-  return ertd_unet_plan_launch_steps(p, p->call.n_run, stream);
+  return ertd_unet_plan_launch_steps(p, p->n_run, stream);
 }
 
 int ertd_unet_plan_destroy(ertd_unet_plan* p) {

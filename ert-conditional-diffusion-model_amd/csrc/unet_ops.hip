@@ -1,7 +1,7 @@
 // Non-conv kernels of the build-defined U-Net (see unet.h): GroupNorm
 // statistics, the small dense layers of the embedding path, the mid-block
-// attention core, the DDPM update, and the step-counter words of a sampler
-// step graph.
+// attention core, the DDPM update and the few-step solver update, and the
+// step-counter words of a sampler step graph.
 #include <cmath>
 
 #include "head_dev.h"  // ddpm_update: the sampler update expression shared with head.hip
@@ -458,6 +458,51 @@ hipError_t launch_unet_update(const UpdateArgs& a, int B, hipStream_t s) {
 
 __global__ void set_word_kernel(int* w, int v) { *w = v; }
 __global__ void dec_word_kernel(int* w) { *w = *w - 1; }
+
+// ---- few-step solver update: the reference model's persistent kernel applies the
+// same device function (head_dev.h solver_update) -----------------------------------
+__global__ void unet_solver_update_kernel(SolverUpdateArgs a, int B) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n = (size_t)B * a.P;
+  if (i >= n) return;
+  const int t = a.words[0], k = a.words[1];
+  if (k < 0 || k >= a.K) return;
+  const int b = (int)(i / a.P), o = (int)(i - (size_t)b * a.P);
+  const SolverRow row = load_solver_row(a.coef, k);
+  // D_prev is zero before the first step (and c_0 == 0): never read there
+  const float dp = row.c != 0.f ? a.d_prev[i] : 0.f;
+  const float z = row.s != 0.f ? solver_noise(a.noise, k, t, B, b, a.P, o, a.seed,
+                                              a.member_offset + (uint32_t)b)
+                               : 0.f;
+  float d;
+  a.x[i] = solver_update(a.x[i], a.eps[i], dp, z, row, a.clip, d);
+  a.d_prev[i] = d;
+}
+
+hipError_t launch_unet_solver_update(const SolverUpdateArgs& a, int B, hipStream_t s) {
+  const size_t n = (size_t)B * a.P;
+  unet_solver_update_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a, B);
+  return hipGetLastError();
+}
+
+__global__ void solver_set_words_kernel(int* w, const int* __restrict__ timesteps, int k) {
+  w[0] = timesteps[k];
+  w[1] = k;
+}
+__global__ void solver_next_words_kernel(int* w, const int* __restrict__ timesteps, int K) {
+  const int k = w[1] + 1;
+  w[1] = k;
+  w[0] = k < K ? timesteps[k] : 0;
+}
+
+hipError_t launch_solver_set_words(int* words, const int* timesteps, int k, hipStream_t s) {
+  solver_set_words_kernel<<<1, 1, 0, s>>>(words, timesteps, k);
+  return hipGetLastError();
+}
+hipError_t launch_solver_next_words(int* words, const int* timesteps, int K, hipStream_t s) {
+  solver_next_words_kernel<<<1, 1, 0, s>>>(words, timesteps, K);
+  return hipGetLastError();
+}
 
 hipError_t launch_set_word(int* w, int v, hipStream_t s) {
   set_word_kernel<<<1, 1, 0, s>>>(w, v);

@@ -11,7 +11,9 @@ from .data import (DeviceDataset, DiffusionDataset, bounds_mask, check_param_bou
 from .model import STATE_KEYS, ConditionalDiffusionModel, get_timestep_embedding, q_sample
 from .sampler import (SamplerPlan, as_ertdiff_model, draw_reference_noise, philox_normal,
                       sample_conditions, sample_model)
-from .schedule import get_diffusion_schedule, step_tables, timestep_frequencies
+from .schedule import (get_diffusion_schedule, solver_tables, spaced_timesteps, step_tables,
+                       timestep_frequencies)
+from .solver import UNetSolverPlan, sample_fast
 from .train import (DiffusionForwardFn, TrainPlan, ValidationPlan, epoch_loss, fit, train_step,
                     validation_loss)
 from .ensemble import member_range, sample_conditions_sharded, sample_ensemble
@@ -41,4 +43,5 @@ __all__ = [
     "uncertainty_metrics", "sort_rows", "wasserstein", "wasserstein_distance", "mse",
     "DeviceDataset", "ValidationPlan", "epoch_loss", "fit",
     "DeviceMinMaxScaler", "prepare_dataset", "split_indices",
+    "sample_fast", "UNetSolverPlan", "spaced_timesteps", "solver_tables",
 ]

@@ -70,6 +70,14 @@ SIGNATURES = {
     "ertd_forward": (_I, [_W, _VP, _VP, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "ertd_sample": (_I, [_W, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP,
                          _VP, _U64, _U32, _I, _I, _VP, _VP, _SZ, _VP]),
+    "ertd_sample_solver": (_I, [_W, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _I, _I, _VP, _VP, _F, _VP,
+                                _VP, _U64, _U32, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "ertd_solver_update": (_I, [_VP, _VP, _VP, _VP, _F, _VP, _I, _I, _VP]),
+    "ertd_unet_sample_solver": (_I, [_VP, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _I, _I, _VP, _VP,
+                                     _F, _VP, _U64, _U32, _VP, _VP, _VP, _SZ, _VP]),
+    "ertd_unet_sample_solver_plan_create": (_I, [_VP, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _I, _I,
+                                                 _VP, _VP, _F, _VP, _U64, _U32, _VP, _VP, _VP, _SZ,
+                                                 _VP, ctypes.POINTER(_VP)]),
     "ertd_philox_normal": (_I, [_U64, _U32, _I, _I, _I, _I, _VP, _VP]),
     "ertd_sample_status": (_I, [_VP, _I, _I, _I, ctypes.POINTER(_I), _VP]),
     "ertd_sample_plan_create": (_I, [_W, _VP, _VP, ctypes.c_longlong, _I, _I, _I, _I, _I, _VP, _VP,

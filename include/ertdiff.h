@@ -149,6 +149,44 @@ int ertd_sample(const ertd_weights* w, const float* packed, const float* cond,
                 const float* noise, uint64_t seed, uint32_t member_offset, int mode,
                 int precision, float* x_inout, void* ws, size_t ws_bytes, void* stream);
 
+/* Few-step sampling on a timestep subset (DDIM, DPM-Solver++(2M)).  For K
+ * descending timesteps tau_0 > ... > tau_{K-1} >= 0 step k is
+ *     eps = model(x, tau_k, cond)
+ *     D   = p_k x + q_k eps;  D = clamp(D, -clip, clip) when clip > 0
+ *     x   = a_k x + b_k D + c_k D_prev + s_k z;   D_prev = D
+ * with D_prev = 0 before step 0.  A term whose coefficient is zero is
+ * skipped: D_prev is not read when c_k == 0, z is neither read nor drawn
+ * when s_k == 0.
+ *   timesteps (K) int32 and coef (K,6) float32, row k = {p,q,a,b,c,s}: DEVICE
+ *     tables (ertdiff.schedule.solver_tables builds them).  They are read back
+ *     once, blocking, on `stream` and refused with ERTD_EINVAL unless the
+ *     timesteps are strictly descending and >= 0, c_0 == 0, every c_k == 0
+ *     when d_prev_inout is NULL, and s_{K-1} == 0 when `noise` is given --
+ *     so the call cannot be captured into a graph.
+ *   Runs steps k = k_first .. k_first+n_run-1.  x_inout (B,P) and
+ *     d_prev_inout (B,P, may be NULL when every c_k == 0) carry the state, so
+ *     a chain split into segments equals the unsplit chain bit for bit
+ *     (d_prev_inout is read only when k_first > 0).
+ *   noise: NULL -> Philox keyed by (seed, member_offset+b, tau_k), the
+ *     ancestral sampler's stream; else (K, B, P): noise[0] = x_T is not read,
+ *     step k reads noise[k+1], the last step reads none.
+ *   mode: ERTD_MODE_HOISTED only (one persistent kernel, x and D_prev in
+ *     registers).  The faithful modes exist to mirror the reference's
+ *     per-step encoder recompute and would give the same bits: ERTD_EINVAL.
+ *   ws: ertd_workspace_bytes(B, L, P, K, ERTD_OP_SAMPLE).                  */
+int ertd_sample_solver(const ertd_weights* w, const float* packed, const float* cond,
+                       long long cond_stride, int B, int L, int K, int k_first, int n_run,
+                       const int32_t* timesteps, const float* coef, float clip, const float* freq,
+                       const float* noise, uint64_t seed, uint32_t member_offset, int mode,
+                       int precision, float* x_inout, float* d_prev_inout, void* ws,
+                       size_t ws_bytes, void* stream);
+/* The bare update of one step on (B,P) device arrays: coef_row = 6 device
+ * floats {p,q,a,b,c,s}.  x in/out; d_prev in/out (may be NULL: treated as
+ * zero, D not stored); z may be NULL (treated as zero).  d_prev is read only
+ * when c != 0, z only when s != 0.                                          */
+int ertd_solver_update(float* x, const float* eps, float* d_prev, const float* coef_row, float clip,
+                       const float* z, int B, int P, void* stream);
+
 /* Status word of the last persistent faithful chain run on `ws` (same B, L,
  * num_steps as the ertd_sample call): synchronizes `stream`; *status = 0 and
  * ERTD_OK, or the code of the wait that timed out and ERTD_ETIMEOUT (the
@@ -488,6 +526,30 @@ int ertd_unet_sample_plan_create(const ertd_unet_config* cfg, const float* packe
                                  int n_run, const float* c1, const float* c2, const float* sigma,
                                  const float* noise, uint64_t seed, uint32_t member_offset,
                                  float* x_inout, void* ws, size_t ws_bytes, ertd_unet_plan** plan);
+/* ertd_sample_solver around the U-Net: steps k = k_first .. k_first+n_run-1 of
+ * the K-step table on x_inout (B, image^2); timesteps / coef / clip / noise /
+ * seed / member_offset as there.  d_prev_inout (B, image^2) is required: the
+ * update kernel stores D every step (and reads it only when c_k != 0).  The
+ * workspace is ertd_unet_workspace_bytes, unchanged: the step counter slot
+ * holds two words, {tau_k, k}.                                             */
+int ertd_unet_sample_solver(const ertd_unet_config* cfg, const float* packed, const float* cond,
+                            long long cond_stride, int L, int B, int K, int k_first, int n_run,
+                            const int32_t* timesteps, const float* coef, float clip,
+                            const float* noise, uint64_t seed, uint32_t member_offset,
+                            float* x_inout, float* d_prev_inout, void* ws, size_t ws_bytes,
+                            void* stream);
+/* The same call as a plan (ertd_unet_plan_launch / _launch_steps / _destroy):
+ * the tables are checked once here, on `stream`; the step graph is captured
+ * once and replayed n_run times, reading {tau_k, k} from the two device
+ * words, which a word kernel at the end of the step advances from the device
+ * timesteps table.  Equal to the eager call bit for bit.                   */
+int ertd_unet_sample_solver_plan_create(const ertd_unet_config* cfg, const float* packed,
+                                        const float* cond, long long cond_stride, int L, int B,
+                                        int K, int k_first, int n_run, const int32_t* timesteps,
+                                        const float* coef, float clip, const float* noise,
+                                        uint64_t seed, uint32_t member_offset, float* x_inout,
+                                        float* d_prev_inout, void* ws, size_t ws_bytes,
+                                        void* stream, ertd_unet_plan** plan);
 int ertd_unet_plan_launch(ertd_unet_plan* plan, void* stream);
 /* head + the first n_steps (0 <= n_steps <= n_run) steps only: warms both
  * graphs (first-launch upload) without running the whole plan.            */
