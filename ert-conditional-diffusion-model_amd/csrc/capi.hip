@@ -119,6 +119,9 @@ int enqueue_sample(const ertd_weights* w, const float* packed, const float* cond
     // rows, each member reads row b % ncond) -- bitwise the rows it would
     // compute per member
     const int nenc = ncond > 0 ? ncond : B;
+    // no wait can time out here, but ertd_sample_status may be asked about any
+    // run on ws: the word holds whatever the caller's memory held, so clear it
+    ERTD_TRY(launch_zero_words(W.status, 1, s));
     ERTD_TRY(launch_encoder_strips(packed, w->enc0_b, w->enc2_b, cond, cstride, nenc, L, precision,
                                    W.partial, s));
     ERTD_TRY(launch_hoist_prep(*w, packed, W.partial, S, L2, nenc, W.U, W.cond_emb, s));
@@ -385,6 +388,7 @@ int ertd_sample_solver(const ertd_weights* w, const float* packed, const float* 
   const int r = solver_tables_ok(timesteps, coef, K, d_prev_inout != nullptr, noise != nullptr, s);
   if (r != ERTD_OK) return r;
   const int L2 = conv_len(conv_len(L)), S = n_strips(L2);
+  ERTD_TRY(launch_zero_words(W.status, 1, s));   // as the hoisted ertd_sample: status reads ok
   ERTD_TRY(launch_encoder_strips(packed, w->enc0_b, w->enc2_b, cond, cond_stride, B, L, precision,
                                  W.partial, s));
   ERTD_TRY(launch_hoist_prep(*w, packed, W.partial, S, L2, B, W.U, W.cond_emb, s));

@@ -524,6 +524,8 @@ hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipS
   if (r.kernel != WinoRoute::NONE) return launch_conv_wino(act, a, s, r);
   if (ks == 3 && mode == MODE_S1 && act == ACT_NONE) return launch_t<3, MODE_S1, ACT_NONE>(a, B, s);
   if (ks == 3 && mode == MODE_S1 && act == ACT_GN_SILU) return launch_t<3, MODE_S1, ACT_GN_SILU>(a, B, s);
+  // GroupNorm without SiLU on a shape no Winograd route takes (Ca % 8 != 0 at B = 2, say)
+  if (ks == 3 && mode == MODE_S1 && act == ACT_GN) return launch_t<3, MODE_S1, ACT_GN>(a, B, s);
   if (ks == 3 && mode == MODE_S2 && act == ACT_NONE) return launch_t<3, MODE_S2, ACT_NONE>(a, B, s);
   if (ks == 3 && mode == MODE_UP && act == ACT_NONE) {
     // sub-pixel: 2x2 taps per class at the source resolution (weights packed

@@ -27,6 +27,7 @@
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -110,6 +111,51 @@ def _adam_state(optimizer, params):
         exp_avg.append(st["exp_avg"])
         exp_avg_sq.append(st["exp_avg_sq"])
     return exp_avg, exp_avg_sq
+
+
+_STEP_BASES = weakref.WeakKeyDictionary()   # optimizer -> the CPU tensor its step counters view
+
+
+def _shared_step_base(optimizer, params):
+    """ONE CPU float32 tensor per optimizer whose elements the 12
+    optimizer.state[p]["step"] counters are views of, shared by every TrainPlan
+    on that optimizer: a replay of any plan bumps it with one add_, and every
+    other plan (and torch.optim.Adam itself, and the eager train_step) reads and
+    bumps the same memory.  Re-made when the state no longer views it
+    (optimizer.load_state_dict replaces the state tensors).  Returns
+    (base, the state's own view tensors)."""
+    base = _STEP_BASES.get(optimizer)
+    steps = [optimizer.state[p]["step"] for p in params]
+    if base is not None and base.numel() == len(params) and all(
+            isinstance(s, torch.Tensor) and s.device.type == "cpu" and s.dtype == torch.float32
+            and s.data_ptr() == base[i].data_ptr() for i, s in enumerate(steps)):
+        return base, steps
+    base = torch.tensor([float(s) for s in steps], dtype=torch.float32)
+    for i, p in enumerate(params):
+        optimizer.state[p]["step"] = base[i]
+    _STEP_BASES[optimizer] = base
+    return base, [optimizer.state[p]["step"] for p in params]
+
+
+def _hp_key(g0):
+    """The optimizer's lr / betas / eps by VALUE: a Tensor lr a scheduler
+    fill_()s in place is the same object with another value."""
+    lr = g0["lr"]
+    return (float(lr) if isinstance(lr, torch.Tensor) else lr, g0["betas"], g0["eps"])
+
+
+def _refuse_device_steps(optimizer, params):
+    """capturable=True / fused=True keep state["step"] on the device, where the
+    plan's host-side step bookkeeping cannot follow it."""
+    g0 = optimizer.param_groups[0]
+    if g0.get("capturable", False) or g0.get("fused", False):
+        raise RuntimeError("ertdiff: TrainPlan needs host step counters; build the optimizer with "
+                           "capturable=False and fused=False")
+    for p in params:
+        s = optimizer.state[p].get("step") if p in optimizer.state else None
+        if isinstance(s, torch.Tensor) and s.device.type != "cpu":
+            raise RuntimeError("ertdiff: TrainPlan needs host step counters; optimizer.state[p]['step'] "
+                               f"is on {s.device}")
 
 
 def train_step(model, optimizer, x0, cond, T, alpha_bar, *, t=None, noise=None,
@@ -283,6 +329,7 @@ class TrainPlan:
         self.dev, self.B, self.L = dev, int(B), int(L)
         P = model.param_dim
         self.lr, self.b1, self.b2, self.eps = _adam_hparams(optimizer, self.params)
+        _refuse_device_steps(optimizer, self.params)
         self.alpha_bar = _lib.f32c(alpha_bar, "alpha_bar")
         # the head kernel draws t in [0, T) and reads alpha_bar[t] on the device:
         # a shorter schedule would read past its end (the reference's
@@ -303,14 +350,11 @@ class TrainPlan:
         self.grads = [p.grad for p in self.params]
         # the 12 step counters become views of ONE CPU tensor: a replay bumps them
         # with one add_ instead of a 12-tensor foreach (host time per step);
-        # torch.optim.Adam reads and bumps state["step"] in place alike
-        self._step_base = torch.tensor([float(optimizer.state[p]["step"]) for p in self.params],
-                                       dtype=torch.float32)
-        for i, p in enumerate(self.params):
-            optimizer.state[p]["step"] = self._step_base[i]
-        self._steps = [optimizer.state[p]["step"] for p in self.params]
-        g0 = optimizer.param_groups[0]
-        self._hp_raw = (g0["lr"], g0["betas"], g0["eps"])
+        # torch.optim.Adam reads and bumps state["step"] in place alike.  The
+        # tensor belongs to the OPTIMIZER, not to the plan: every plan on one
+        # optimizer (one per sequence length L) counts the same steps
+        self._step_base, self._steps = _shared_step_base(optimizer, self.params)
+        self._hp_raw = _hp_key(optimizer.param_groups[0])
         self.ws = torch.empty(max(_lib.lib().ertd_workspace_bytes(B, L, P, 0, _lib.OP_TRAIN), 256),
                               dtype=torch.uint8, device=dev)
         self.freq = timestep_frequencies(_lib.HIDDEN, dev)
@@ -400,18 +444,19 @@ class TrainPlan:
         user's optimizer.step()) -- the step counters are host tensors -- and
         edits of the optimizer's lr / betas / eps (a scheduler): the table of
         Adam scalars is rebuilt from the current hyper-parameters."""
-        g0 = self.optimizer.param_groups[0]
-        raw = (g0["lr"], g0["betas"], g0["eps"])
+        raw = _hp_key(self.optimizer.param_groups[0])
         if raw != self._hp_raw:
             self._hp_raw = raw
             hp = _adam_hparams(self.optimizer, self.params)
             if hp != (self.lr, self.b1, self.b2, self.eps):
                 self.lr, self.b1, self.b2, self.eps = hp
                 self._table_at(self.host_step)
-        st = self._steps[0]
-        if st.device.type != "cpu":
-            return
-        s = int(st.item())
+        if self.optimizer.state[self.params[0]]["step"] is not self._steps[0]:
+            # the state tensors were replaced (another plan re-made the shared
+            # base after a load_state_dict): count on the live ones
+            _refuse_device_steps(self.optimizer, self.params)
+            self._step_base, self._steps = _shared_step_base(self.optimizer, self.params)
+        s = int(self._steps[0].item())
         if s != self.host_step:
             if self.table_first <= s + 1 < self.table_first + self.TABLE:
                 self.step_dev.fill_(s)

@@ -18,6 +18,30 @@
  *   - return 0 on success, a negative ERTD_E* code for bad arguments (checked
  *     on the host BEFORE anything is launched), or a positive hipError_t.
  *
+ * Workspace contract (every entry that takes `ws, ws_bytes`, and every output;
+ * tests/test_gpu_dirty_entries.py and test_gpu_dirty_api.py enforce it on
+ * 0xFF-filled, exactly sized, fenced memory):
+ *   - the contents of ws and of every output on entry are ARBITRARY: no entry
+ *     relies on zeros, and nothing is read before the same call has written
+ *     it (counters, ring / claim / progress words, partial-sum buffers, pad
+ *     lanes of packed weights and of the bf16 image are all written first);
+ *   - nothing outside [ws, ws + ws_bytes) and outside the outputs is written,
+ *     and nothing outside the inputs as described is read; ws_bytes equal to
+ *     the entry's *_ws_bytes / *_workspace_bytes query is enough, one byte
+ *     less is ERTD_ENOSPC with nothing launched and no output touched;
+ *   - results do not depend on what ws held: a call on a workspace another
+ *     call (another geometry, another entry) has used gives the same bits.
+ * The ONLY state carried from one call to the next:
+ *   - the packing at the head of ws that ertd_conv2d / ertd_conv_input_grad
+ *     (or ertd_conv_pack_batch) leave for the *_run entries;
+ *   - the activations ertd_train_forward / ertd_encoder_train_fwd save in ws
+ *     for the matching backward;
+ *   - a plan's workspace and bound buffers between its launches (head graph
+ *     -> step graphs; a plan never shares ws with another stream's work);
+ *   - the sampler status word (ertd_sample_status), which EVERY ertd_sample /
+ *     ertd_sample_conditions / ertd_sample_solver call clears or sets, the
+ *     hoisted mode included.
+ *
  * Shapes: B = batch (members), L = measurements per survey (4693 in the
  * reference), C_in = 14 surveys, P = param_dim (29 in the reference, 1..32
  * supported), H = hidden_dim (128; the only value the reference uses).

@@ -315,3 +315,108 @@ def test_train_plan_run_multistep_graph_equals_steps(golden_weights, cuda_dev):
         s1, s2 = os_[0].state[p1], os_[1].state[p2]
         assert float(s1["step"]) == float(s2["step"]) == 43.0, k
         assert torch.equal(s1["exp_avg"], s2["exp_avg"]) and torch.equal(s1["exp_avg_sq"], s2["exp_avg_sq"]), k
+
+
+def _state_equal(m1, o1, m2, o2, steps):
+    for (k, p1), p2 in zip(m1.named_parameters(), m2.parameters()):
+        assert torch.equal(p1, p2), k
+        s1, s2 = o1.state[p1], o2.state[p2]
+        assert float(s1["step"]) == float(s2["step"]) == float(steps), (k, float(s1["step"]), float(s2["step"]))
+        assert torch.equal(s1["exp_avg"], s2["exp_avg"]), k
+        assert torch.equal(s1["exp_avg_sq"], s2["exp_avg_sq"]), k
+
+
+def test_two_train_plans_share_one_optimizer(golden_weights, cuda_dev):
+    """One plan per sequence length L on ONE model and Adam, interleaved A, B,
+    A, B with injected t and noise: parameters, both moments and every
+    optimizer.state[p]["step"] equal four eager train_step calls on a twin,
+    bit for bit.  (Each plan once counted its own steps: the second never saw
+    the first's, and repeated Adam step numbers.)"""
+    T, B = 500, 3
+    _, _, ab = ertdiff.get_diffusion_schedule(T, device=cuda_dev)
+    data = {L: _train_inputs(B, L, T, 700 + L, cuda_dev) for L in (37, 9)}
+    m1 = _fresh_model(golden_weights, cuda_dev)
+    o1 = torch.optim.Adam(m1.parameters(), lr=1e-4)
+    m2 = _fresh_model(golden_weights, cuda_dev)
+    o2 = torch.optim.Adam(m2.parameters(), lr=1e-4)
+    plans = {L: ertdiff.TrainPlan(m2, o2, B, L, T, ab) for L in (37, 9)}
+    for i, L in enumerate((37, 9, 37, 9)):
+        x0, cond, ts, ns = data[L]
+        la = ertdiff.train_step(m1, o1, x0, cond, T, ab, t=ts[i], noise=ns[i])
+        lb = plans[L].step(x0, cond, t=ts[i], noise=ns[i])
+        assert la == lb, (i, L, la, lb)
+        _state_equal(m1, o1, m2, o2, i + 1)
+    # an eager step between replays is counted by both plans as well
+    x0, cond, ts, ns = data[9]
+    for m, o in ((m1, o1), (m2, o2)):
+        ertdiff.train_step(m, o, x0, cond, T, ab, t=ts[0], noise=ns[0])
+    x0, cond, ts, ns = data[37]
+    assert ertdiff.train_step(m1, o1, x0, cond, T, ab, t=ts[1], noise=ns[1]) == \
+        plans[37].step(x0, cond, t=ts[1], noise=ns[1])
+    _state_equal(m1, o1, m2, o2, 6)
+
+
+def test_two_train_plans_philox_draws_follow_the_shared_step(golden_weights, cuda_dev):
+    """rng="philox" keys the draws by (seed, member, Adam step): two plans with
+    one seed on one optimizer, interleaved, draw what a single plan draws at
+    steps 1..4 -- the draws of step k, not a repeat of step k - 1's."""
+    T, B, seed = 1000, 3, 4321
+    _, _, ab = ertdiff.get_diffusion_schedule(T, device=cuda_dev)
+    x0a, conda, _, _ = _train_inputs(B, 37, T, 720, cuda_dev)
+    x0b, condb, _, _ = _train_inputs(B, 9, T, 730, cuda_dev)
+    m1 = _fresh_model(golden_weights, cuda_dev)
+    solo = ertdiff.TrainPlan(m1, torch.optim.Adam(m1.parameters(), lr=1e-4), B, 37, T, ab, seed=seed)
+    want = []
+    for _ in range(4):
+        solo.step(x0a, conda)
+        want.append((solo.t.clone(), solo.noise.clone()))
+    assert not torch.equal(want[0][1], want[1][1])
+    m2 = _fresh_model(golden_weights, cuda_dev)
+    o2 = torch.optim.Adam(m2.parameters(), lr=1e-4)
+    pa = ertdiff.TrainPlan(m2, o2, B, 37, T, ab, seed=seed)
+    pb = ertdiff.TrainPlan(m2, o2, B, 9, T, ab, seed=seed)
+    for k, (plan, x0, cond) in enumerate(((pa, x0a, conda), (pb, x0b, condb), (pa, x0a, conda), (pb, x0b, condb))):
+        plan.step(x0, cond)
+        assert torch.equal(plan.t, want[k][0]) and torch.equal(plan.noise, want[k][1]), k
+    assert all(float(o2.state[p]["step"]) == 4.0 for p in m2.parameters())
+
+
+def test_train_plan_follows_tensor_lr_filled_in_place(golden_weights, cuda_dev):
+    """A Tensor lr that a scheduler updates with fill_() is the same object with
+    another value: the plan compares values and rebuilds its Adam table."""
+    B, L, T = 3, 37, 500
+    x0, cond, ts, ns = _train_inputs(B, L, T, 740, cuda_dev)
+    _, _, ab = ertdiff.get_diffusion_schedule(T, device=cuda_dev)
+    m1 = _fresh_model(golden_weights, cuda_dev)
+    o1 = torch.optim.Adam(m1.parameters(), lr=1e-3)
+    m2 = _fresh_model(golden_weights, cuda_dev)
+    o2 = torch.optim.Adam(m2.parameters(), lr=1e-4)
+    lr = torch.tensor(1e-3)
+    o2.param_groups[0]["lr"] = lr
+    plan = ertdiff.TrainPlan(m2, o2, B, L, T, ab)
+    for i, v in enumerate((1e-3, 5e-4)):
+        lr.fill_(v)
+        o1.param_groups[0]["lr"] = float(lr)     # the eager twin gets the value the tensor holds
+        la = ertdiff.train_step(m1, o1, x0, cond, T, ab, t=ts[i], noise=ns[i])
+        lb = plan.step(x0, cond, t=ts[i], noise=ns[i])
+        assert la == lb, (i, la, lb)
+        _state_equal(m1, o1, m2, o2, i + 1)
+
+
+@pytest.mark.parametrize("kw", [{"capturable": True}, {"fused": True}])
+def test_train_plan_refuses_device_resident_steps(kw, golden_weights, cuda_dev):
+    """capturable=True / fused=True keep optimizer.state[p]["step"] on the
+    device, where the plan's host-side step bookkeeping cannot follow it:
+    refused at construction, before or after the optimizer made its state."""
+    B, L, T = 2, 9, 100
+    _, _, ab = ertdiff.get_diffusion_schedule(T, device=cuda_dev)
+    m = _fresh_model(golden_weights, cuda_dev)
+    opt = torch.optim.Adam(m.parameters(), lr=1e-4, **kw)
+    with pytest.raises(RuntimeError, match="host step counters"):
+        ertdiff.TrainPlan(m, opt, B, L, T, ab)
+    for p in m.parameters():
+        p.grad = torch.zeros_like(p)
+    opt.step()                                   # state["step"] now lives on the device
+    assert next(iter(opt.state.values()))["step"].is_cuda
+    with pytest.raises(RuntimeError, match="host step counters"):
+        ertdiff.TrainPlan(m, opt, B, L, T, ab)
