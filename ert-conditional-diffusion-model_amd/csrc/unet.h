@@ -370,9 +370,22 @@ __device__ __forceinline__ void gn_fold_item_done(const GnFold& f, int b, int* l
   }
 }
 
+// The kernel launch_conv runs for (ks, mode, act, a, B) and the persistent
+// launch's geometry: the one decision launch_conv switches on, and what
+// ertd_conv2d_route_info reports (pointers of `a` are tested for null, never
+// dereferenced).  kernel: ERTD_ROUTE_* (include/ertdiff.h), -1 = no kernel
+// takes the call (launch_conv returns hipErrorInvalidValue).
+struct ConvDispatch {
+  int kernel = -1;
+  WinoRoute route;           // fp32 3x3: the Winograd route (kernel NONE otherwise)
+  int items = 0, grid = 0;   // persistent kernels: work items and workgroups (else 0, 0)
+};
+ConvDispatch conv_dispatch(int ks, int mode, int act, const ConvArgs& a, int B);
 hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s);
 // bf16-operand variant (unet_conv_bf16.hip): same arguments, wpk packed by
-// launch_pack_conv_bf16
+// launch_pack_conv_bf16; conv_bf16_dispatch: the kernel it runs (ERTD_ROUTE_CONV_OUT /
+// _CONV_IN / _BF16; none of them persistent)
+int conv_bf16_dispatch(int ks, int mode, int act, const ConvArgs& a);
 hipError_t launch_conv_bf16(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s);
 // split: the split-bf16 layouts (two bf16 planes, hi and lo = RNE(x - hi))
 size_t conv_packed_floats_bf16(int cin, int cout, int ks, bool split = false);
@@ -415,7 +428,14 @@ bool conv1x1_ok(const ConvArgs& a, int act, int B);
 hipError_t launch_conv1x1(const ConvArgs& a, int B, hipStream_t s);
 // the 1x1 skip convs as a batched GEMM on 32x32x2 fp32 MFMAs (unet_skip_gemm.hip)
 bool skip_gemm_ok(const ConvArgs& a, int ks, int mode, int act, int B);
-hipError_t launch_skip_gemm(const ConvArgs& a, int B, hipStream_t s);
+// geom non-null: nothing is launched; *geom = the launch's kernel, tile and
+// persistent geometry (the launchers' own ntiles and occupancy-derived cap)
+struct SkipGemmGeom {
+  bool split = false;        // the split-bf16 kernel (else the fp32 one)
+  int mt = 0, nt = 0;        // tile: output channels x pixels
+  int items = 0, grid = 0;   // tiles and workgroups
+};
+hipError_t launch_skip_gemm(const ConvArgs& a, int B, hipStream_t s, SkipGemmGeom* geom = nullptr);
 // training: the fp32 3x3 stride-1 weight gradient by Winograd F(4x4,3x3)
 // (unet_wgrad_wino.hip); scratch floats it needs (0 = not eligible: Cin, Cout
 // multiples of 64, H in {16, 32, 64}; ERTD_WGRAD_WINO=0 disables)

@@ -1010,6 +1010,30 @@ size_t ertd_conv2d_workspace_bytes(int cin, int cout, int ks, int precision, int
 }
 
 namespace {
+// The ConvArgs of an ertd_conv2d call whose workspace starts at pk: the
+// operands, the geometry, the packing the routed kernel reads and the caller-
+// owned scratch behind it (stream-ordered: reused by the next call).  No
+// pointer is dereferenced here: ertd_conv2d_route_info passes placeholders.
+ConvArgs conv2d_args(const float* x, int Ca, const float* x2, int Cb, int H, const float* bias, int Cout,
+                     int ks, int mode, const float* gn, const float* ebias, int eb_stride, const float* res,
+                     float* out, int precision, float* pk, const Conv2dWs& need, const WinoRoute& route) {
+  const int Cin = Ca + Cb;
+  ConvArgs a{};
+  a.srcA = x; a.srcB = x2; a.Ca = Ca; a.Cb = Cb;
+  a.gn = (const float2*)gn;
+  a.wpk = pk; a.bias = bias; a.ebias = ebias; a.eb_stride = eb_stride; a.res = res; a.out = out;
+  a.Cin = Cin; a.Cout = Cout; a.Hs = H; a.Ws = H;
+  a.Ho = a.Wo = conv2d_out_size(H, mode);
+  if (route.kernel != WinoRoute::NONE) {
+    float* pw = pk + a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
+    if (route.pack_kind == ERTD_PACK_WINO4) a.wpk_wino4 = pw; else a.wpk_wino = pw;
+    a.ksplit_buf = need.kbuf_floats ? pk + a64(need.pack_floats) : nullptr;
+  }
+  a.bimg = need.bimg_bytes ? (void*)(pk + a64(need.pack_floats) + a64(need.kbuf_floats)) : nullptr;
+  a.split = precision == ERTD_PREC_BF16X3 ? 1 : 0;
+  return a;
+}
+
 // ertd_conv2d: pack (unless `pack` is false: ws already holds this shape's
 // packing from an earlier call) and launch; gnp (B, Cout, gn_np) float2: the
 // GroupNorm partials of the output from the epilogue (gn_np must be what
@@ -1027,9 +1051,6 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
   if (need.total() > ws_bytes) return ERTD_ENOSPC;
   hipStream_t s = (hipStream_t)stream;
   float* pk = (float*)ws;
-  // caller-owned scratch behind the packing (stream-ordered: reused by the next call)
-  float* kbuf = need.kbuf_floats ? pk + a64(need.pack_floats) : nullptr;
-  void* bimg = need.bimg_bytes ? (void*)(pk + a64(need.pack_floats) + a64(need.kbuf_floats)) : nullptr;
   // the Winograd path reads only its own packing: skip the direct one then
   const bool bf = bf_prec(precision), split = precision == ERTD_PREC_BF16X3;
   const WinoRoute route = conv2d_route(Cin, Ca, Cout, ks, mode, act, precision, B, H);
@@ -1041,22 +1062,12 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
         : (ks == 3 && mode == MODE_UP) ? launch_pack_conv_up(w, Cin, Cout, pk, s)
                                        : launch_pack_conv(w, Cin, Cout, ks, pk, s);
   if (e != hipSuccess) return (int)e;
-  ConvArgs a{};
-  a.srcA = x; a.srcB = x2; a.Ca = Ca; a.Cb = Cb;
-  a.gn = (const float2*)gn;
-  a.wpk = pk; a.bias = bias; a.ebias = ebias; a.eb_stride = eb_stride; a.res = res; a.out = out;
-  a.Cin = Cin; a.Cout = Cout; a.Hs = H; a.Ws = H;
-  a.Ho = a.Wo = conv2d_out_size(H, mode);
-  if (wino) {
-    float* pw = pk + a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
-    if (pack && (e = wino4 ? launch_pack_conv_wino4(w, Cin, Cout, pw, s)
-                           : launch_pack_conv_wino(w, Cin, Cout, pw, s)) != hipSuccess)
-      return (int)e;
-    if (wino4) a.wpk_wino4 = pw; else a.wpk_wino = pw;
-    a.ksplit_buf = kbuf;
-  }
-  a.bimg = bimg;
-  a.split = split ? 1 : 0;
+  ConvArgs a = conv2d_args(x, Ca, x2, Cb, H, bias, Cout, ks, mode, gn, ebias, eb_stride, res, out, precision,
+                           pk, need, route);
+  if (wino && pack &&
+      (e = wino4 ? launch_pack_conv_wino4(w, Cin, Cout, const_cast<float*>(a.wpk_wino4), s)
+                 : launch_pack_conv_wino(w, Cin, Cout, const_cast<float*>(a.wpk_wino), s)) != hipSuccess)
+    return (int)e;
   if (gnp) {
     if (conv_gn_parts(ks, mode, act, a, route) != gn_np) return ERTD_EINVAL;
     a.gnp = (float2*)gnp;
@@ -1092,6 +1103,37 @@ int ertd_conv2d_gn_parts(int Ca, int Cb, int Cout, int ks, int mode, int act, in
   q.Hs = q.Ws = H;
   q.Ho = q.Wo = conv2d_out_size(H, mode);
   return conv_gn_parts(ks, mode, act, q, conv2d_route(Cin, Ca, Cout, ks, mode, act, precision, B, H));
+}
+
+int ertd_conv2d_route_info(int Ca, int Cb, int Cout, int ks, int mode, int act, int precision, int has_ebias,
+                           int B, int H, ertd_route_info* out) {
+  const int Cin = Ca + Cb;
+  if (!out || Ca < 1 || Cb < 0 || !conv2d_geom_ok(Cin, Cout, ks, precision, B, H, mode) || act < ACT_NONE ||
+      act > ACT_GN)
+    return ERTD_EINVAL;
+  // the call's ConvArgs with placeholder operands (the dispatch tests them for
+  // null, nothing dereferences them): a workspace at `base`, every operand the
+  // call has somewhere non-null
+  float* const base = reinterpret_cast<float*>((uintptr_t)4096);
+  const Conv2dWs need = conv2d_ws(Cin, Ca, Cout, ks, precision, B, H, mode, act);
+  const WinoRoute route = conv2d_route(Cin, Ca, Cout, ks, mode, act, precision, B, H);
+  const ConvArgs a = conv2d_args(base, Ca, Cb > 0 ? base : nullptr, Cb, H, base, Cout, ks, mode,
+                                 act != ACT_NONE ? base : nullptr, (has_ebias & 1) ? base : nullptr, Cout,
+                                 (has_ebias & 2) ? base : nullptr, base, precision, base, need, route);
+  *out = ertd_route_info{};
+  out->ksplit = 1;
+  if (bf_prec(precision)) {
+    out->kernel = conv_bf16_dispatch(ks, mode, act, a);
+  } else {
+    const ConvDispatch d = conv_dispatch(ks, mode, act, a, B);
+    if (d.kernel < 0) return ERTD_EINVAL;
+    out->kernel = d.kernel;
+    out->items = d.items;
+    out->grid = d.grid;
+    if (d.route.kernel != WinoRoute::NONE) out->ksplit = d.route.ksplit;
+  }
+  out->gn_parts = ertd_conv2d_gn_parts(Ca, Cb, Cout, ks, mode, act, precision, B, H);
+  return ERTD_OK;
 }
 
 int ertd_conv2d_gn(const float* x, int Ca, const float* x2, int Cb, int B, int H, const float* w,

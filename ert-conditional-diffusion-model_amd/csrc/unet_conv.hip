@@ -508,38 +508,91 @@ int conv_gn_parts(int ks, int mode, int act, const ConvArgs& a, const WinoRoute&
   return r.gn_parts;
 }
 
-hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s) {
-  if (a.Ho != a.Wo || a.Hs != a.Ws || a.Cin != a.Ca + a.Cb) return hipErrorInvalidValue;
+// the direct implicit-GEMM instantiations: (ks, mode, act) they exist for
+static bool direct_ok(int ks, int mode, int act) {
+  if (ks == 3 && mode == MODE_S1) return act == ACT_NONE || act == ACT_GN_SILU || act == ACT_GN;
+  if (ks == 3 && mode == MODE_S2) return act == ACT_NONE;
+  return ks == 1 && mode == MODE_S1 && (act == ACT_NONE || act == ACT_GN);
+}
+
+// The dispatch, in the order of precedence: conv_out, conv_in, the Winograd
+// route, the direct 3x3 kernels, the sub-pixel Upsample conv, the skip GEMMs,
+// the LDS-DMA 1x1 kernel, the direct 1x1 kernels.
+ConvDispatch conv_dispatch(int ks, int mode, int act, const ConvArgs& a, int B) {
+  ConvDispatch d;
+  if (a.Ho != a.Wo || a.Hs != a.Ws || a.Cin != a.Ca + a.Cb) return d;
   const int expect = mode == MODE_S2 ? a.Ws / 2 : (mode == MODE_UP ? a.Ws * 2 : a.Ws);
-  if (a.Wo != expect) return hipErrorInvalidValue;
-  const WinoRoute r = ks == 3 ? wino_route(mode, act, a.Cin, a.Ca, a.Cout, a.Wo, B, a.wpk_wino != nullptr,
-                                           a.wpk_wino4 != nullptr, device_cu_count())
-                              : WinoRoute{};
+  if (a.Wo != expect) return d;
+  if (ks == 3)
+    d.route = wino_route(mode, act, a.Cin, a.Ca, a.Cout, a.Wo, B, a.wpk_wino != nullptr, a.wpk_wino4 != nullptr,
+                         device_cu_count());
+  if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN) {
+    d.kernel = ERTD_ROUTE_CONV_OUT;
+  } else if (conv_in_ok(a, ks, mode, act)) {
+    d.kernel = ERTD_ROUTE_CONV_IN;
+  } else if (d.route.kernel != WinoRoute::NONE) {
+    switch (d.route.kernel) {
+      case WinoRoute::F2: d.kernel = ERTD_ROUTE_F2; break;
+      case WinoRoute::F4: d.kernel = ERTD_ROUTE_F4; break;
+      case WinoRoute::F4S: d.kernel = ERTD_ROUTE_F4S; break;
+      default: d.kernel = ERTD_ROUTE_F4S_UP; break;
+    }
+    d.items = d.route.items;
+    d.grid = d.route.grid;
+  } else if (ks == 3 && direct_ok(ks, mode, act)) {
+    // (ACT_GN: GroupNorm without SiLU on a shape no Winograd route takes, Ca % 8 != 0 at B = 2, say)
+    d.kernel = ERTD_ROUTE_DIRECT;
+  } else if (ks == 3 && mode == MODE_UP && act == ACT_NONE) {
+    if (a.Ws == 16 || a.Ws == 32 || a.Ws == 64) d.kernel = ERTD_ROUTE_UP;
+  } else if (skip_gemm_ok(a, ks, mode, act, B)) {
+    SkipGemmGeom g;
+    if (launch_skip_gemm(a, B, nullptr, &g) != hipSuccess) return d;
+    d.kernel = g.split ? ERTD_ROUTE_SKIP_GEMM_SPLIT : ERTD_ROUTE_SKIP_GEMM;
+    d.items = g.items;
+    d.grid = g.grid;
+  } else if (ks == 1 && mode == MODE_S1 && act == ACT_NONE && conv1x1_ok(a, act, B)) {
+    d.kernel = ERTD_ROUTE_CONV1X1;
+  } else if (ks == 1 && direct_ok(ks, mode, act)) {
+    d.kernel = ERTD_ROUTE_DIRECT;
+  }
+  return d;
+}
+
+hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s) {
+  const ConvDispatch d = conv_dispatch(ks, mode, act, a, B);
+  if (d.kernel < 0) return hipErrorInvalidValue;
+  const WinoRoute& r = d.route;
   if (a.gnp && conv_gn_parts(ks, mode, act, a, r) == 0) return hipErrorInvalidValue;
   if (a.fold.cnt && (!a.gnp || a.fold.g.pa != a.gnp || !r.fold_ok)) return hipErrorInvalidValue;
   if (a.gnc.pa && (act == ACT_NONE || !wino_gnc_ok(r, a.Cin, a.Wo, a.gnc))) return hipErrorInvalidValue;
-  if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN)
-    return launch_conv_out(act, a, B, PK_F32, s);
-  if (conv_in_ok(a, ks, mode, act)) return launch_conv_in(a, B, PK_F32, s);
-  if (r.kernel != WinoRoute::NONE) return launch_conv_wino(act, a, s, r);
+  switch (d.kernel) {
+    case ERTD_ROUTE_CONV_OUT: return launch_conv_out(act, a, B, PK_F32, s);
+    case ERTD_ROUTE_CONV_IN: return launch_conv_in(a, B, PK_F32, s);
+    case ERTD_ROUTE_F2:
+    case ERTD_ROUTE_F4:
+    case ERTD_ROUTE_F4S:
+    case ERTD_ROUTE_F4S_UP: return launch_conv_wino(act, a, s, r);
+    case ERTD_ROUTE_UP: {
+      // sub-pixel: 2x2 taps per class at the source resolution (weights packed
+      // by launch_pack_conv_up); the template width is the SOURCE width
+      const bool w2 = a.Cout >= 128 && conv_wco_override() != 1;
+      switch (a.Ws) {
+        case 16: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 16>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 16>(a, B, s);
+        case 32: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 32>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 32>(a, B, s);
+        case 64: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 64>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 64>(a, B, s);
+        default: return hipErrorInvalidValue;
+      }
+    }
+    case ERTD_ROUTE_SKIP_GEMM:
+    case ERTD_ROUTE_SKIP_GEMM_SPLIT: return launch_skip_gemm(a, B, s);
+    case ERTD_ROUTE_CONV1X1: return launch_conv1x1(a, B, s);
+    default: break;
+  }
+  // ERTD_ROUTE_DIRECT (direct_ok)
   if (ks == 3 && mode == MODE_S1 && act == ACT_NONE) return launch_t<3, MODE_S1, ACT_NONE>(a, B, s);
   if (ks == 3 && mode == MODE_S1 && act == ACT_GN_SILU) return launch_t<3, MODE_S1, ACT_GN_SILU>(a, B, s);
-  // GroupNorm without SiLU on a shape no Winograd route takes (Ca % 8 != 0 at B = 2, say)
   if (ks == 3 && mode == MODE_S1 && act == ACT_GN) return launch_t<3, MODE_S1, ACT_GN>(a, B, s);
   if (ks == 3 && mode == MODE_S2 && act == ACT_NONE) return launch_t<3, MODE_S2, ACT_NONE>(a, B, s);
-  if (ks == 3 && mode == MODE_UP && act == ACT_NONE) {
-    // sub-pixel: 2x2 taps per class at the source resolution (weights packed
-    // by launch_pack_conv_up); the template width is the SOURCE width
-    const bool w2 = a.Cout >= 128 && conv_wco_override() != 1;
-    switch (a.Ws) {
-      case 16: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 16>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 16>(a, B, s);
-      case 32: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 32>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 32>(a, B, s);
-      case 64: return w2 ? launch_p<2, MODE_UPP, ACT_NONE, 2, 64>(a, B, s) : launch_p<2, MODE_UPP, ACT_NONE, 1, 64>(a, B, s);
-      default: return hipErrorInvalidValue;
-    }
-  }
-  if (skip_gemm_ok(a, ks, mode, act, B)) return launch_skip_gemm(a, B, s);
-  if (ks == 1 && mode == MODE_S1 && act == ACT_NONE && conv1x1_ok(a, act, B)) return launch_conv1x1(a, B, s);
   if (ks == 1 && mode == MODE_S1 && act == ACT_NONE) return launch_t<1, MODE_S1, ACT_NONE>(a, B, s);
   if (ks == 1 && mode == MODE_S1 && act == ACT_GN) return launch_t<1, MODE_S1, ACT_GN>(a, B, s);
   return hipErrorInvalidValue;

@@ -855,17 +855,24 @@ int conv_bf16_gn_parts(int ks, int mode, int act, const ConvArgs& a, int B) {
   return a.Wo * a.Wo / 64;
 }
 
+// conv_in / conv_out are fp32-VALU kernels: bf16 rounds their operands,
+// split bf16 reads hi + lo weights and keeps the activation fp32
+int conv_bf16_dispatch(int ks, int mode, int act, const ConvArgs& a) {
+  if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN) return ERTD_ROUTE_CONV_OUT;
+  if (conv_in_ok(a, ks, mode, act)) return ERTD_ROUTE_CONV_IN;
+  return ERTD_ROUTE_BF16;
+}
+
 hipError_t launch_conv_bf16(int ks, int mode, int act, const ConvArgs& a, int B, hipStream_t s) {
   if (a.fold.cnt || a.gnc.pa) return hipErrorInvalidValue;   // the fold rides on the fp32 Winograd kernels only
   if (a.Ho != a.Wo || a.Hs != a.Ws || a.Cin != a.Ca + a.Cb) return hipErrorInvalidValue;
   if (a.gnp && (!a.bimg || conv_bf16_gn_parts(ks, mode, act, a, B) == 0)) return hipErrorInvalidValue;
   const int expect = mode == MODE_S2 ? a.Ws / 2 : (mode == MODE_UP ? a.Ws * 2 : a.Ws);
   if (a.Wo != expect) return hipErrorInvalidValue;
-  // conv_in / conv_out are fp32-VALU kernels: bf16 rounds their operands,
-  // split bf16 reads hi + lo weights and keeps the activation fp32
   const int pk = a.split ? 2 : 1;
-  if (a.Cout == 1 && ks == 3 && mode == MODE_S1 && act != ACT_GN) return launch_conv_out(act, a, B, pk, s);
-  if (conv_in_ok(a, ks, mode, act)) return launch_conv_in(a, B, pk, s);
+  const int kernel = conv_bf16_dispatch(ks, mode, act, a);
+  if (kernel == ERTD_ROUTE_CONV_OUT) return launch_conv_out(act, a, B, pk, s);
+  if (kernel == ERTD_ROUTE_CONV_IN) return launch_conv_in(a, B, pk, s);
   return a.split ? launch_conv_h<2>(ks, mode, act, a, B, s) : launch_conv_h<1>(ks, mode, act, a, B, s);
 }
 

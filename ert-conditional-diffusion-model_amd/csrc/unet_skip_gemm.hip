@@ -196,14 +196,19 @@ __global__ __launch_bounds__(SG_THREADS, 2) void skip_gemm_kernel(ConvArgs a, in
 }
 
 template <int MT, int NT>
-hipError_t launch_sg(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_sg(const ConvArgs& a, int B, hipStream_t s, SkipGemmGeom* geom) {
   using G = SgGeom<MT, NT>;
   const int HW = a.Ho * a.Wo;
   static std::atomic<unsigned long long> attr{0};
   set_max_lds_once((const void*)skip_gemm_kernel<MT, NT>, (int)G::LDS, attr);
   const int ntiles = HW / NT * ((a.Cout + MT - 1) / MT) * B;
   const int cap = 2 * device_cu_count();                 // two workgroups per CU (LDS)
-  skip_gemm_kernel<MT, NT><<<ntiles < cap ? ntiles : cap, SG_THREADS, G::LDS, s>>>(a, HW, ntiles);
+  const int grid = ntiles < cap ? ntiles : cap;
+  if (geom) {   // the query: this launch's geometry, nothing launched
+    *geom = SkipGemmGeom{false, MT, NT, ntiles, grid};
+    return hipSuccess;
+  }
+  skip_gemm_kernel<MT, NT><<<grid, SG_THREADS, G::LDS, s>>>(a, HW, ntiles);
   return hipGetLastError();
 }
 
@@ -487,7 +492,7 @@ __global__ __launch_bounds__(NW * 64) void skip_gemm_split_kernel(ConvArgs a, in
 }
 
 template <int MT, int NT, int KC, int NW>
-hipError_t launch_ss(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_ss(const ConvArgs& a, int B, hipStream_t s, SkipGemmGeom* geom) {
   using G = SsGeom<MT, NT, KC, NW>;
   const int HW = a.Ho * a.Wo;
   static std::atomic<unsigned long long> attr{0};
@@ -503,7 +508,12 @@ hipError_t launch_ss(const ConvArgs& a, int B, hipStream_t s) {
   }
   const int ntiles = HW / NT * (a.Cout / MT) * B;
   const int cap = wpc * device_cu_count();
-  skip_gemm_split_kernel<MT, NT, KC, NW><<<ntiles < cap ? ntiles : cap, G::NTHR, G::LDS, s>>>(a, HW, ntiles);
+  const int grid = ntiles < cap ? ntiles : cap;
+  if (geom) {   // the query: this launch's geometry, nothing launched
+    *geom = SkipGemmGeom{true, MT, NT, ntiles, grid};
+    return hipSuccess;
+  }
+  skip_gemm_split_kernel<MT, NT, KC, NW><<<grid, G::NTHR, G::LDS, s>>>(a, HW, ntiles);
   return hipGetLastError();
 }
 
@@ -553,7 +563,9 @@ static bool sg_tile(const ConvArgs& a, int B, int& mt, int& nt) {
 
 // The split-bf16 kernel's tile: 128 x 128 where Cout is a multiple of 128, else
 // 64 x 256 (the Cout = 64 skips at 64 x 64), 64 x 128 where 256 pixels do not
-// divide HW.  Independent of B: a sample's bits do not depend on the batch.
+// divide HW.  Independent of B: a sample's bits do not depend on the batch --
+// nor on the tile, round or workgroup of the persistent walk that computes it
+// (the placement invariance stated at ertd_conv2d_route_info, include/ertdiff.h).
 // false: the shape stays on the fp32 kernels.
 constexpr int SS_KC = 32, SS_NW = 8;    // channels per chunk, waves per workgroup
 static bool ss_tile(const ConvArgs& a, int& mt, int& nt) {
@@ -573,15 +585,15 @@ static bool ss_tile(const ConvArgs& a, int& mt, int& nt) {
 }
 
 template <int MT, int NT>
-static hipError_t launch_ss_tile(const ConvArgs& a, int B, hipStream_t s) {
+static hipError_t launch_ss_tile(const ConvArgs& a, int B, hipStream_t s, SkipGemmGeom* geom) {
 #ifdef ERTD_DIAG
   // ERTD_SGS_KC = 16 / 32, ERTD_SGS_NW = 4 / 8: the schedule variants for A/B
   static const int kc = ERTD_KNOB("SGS_KC", SS_KC), nw = ERTD_KNOB("SGS_NW", SS_NW);
-  if (kc == 16 && nw == 4) return launch_ss<MT, NT, 16, 4>(a, B, s);
-  if (kc == 16 && nw == 8) return launch_ss<MT, NT, 16, 8>(a, B, s);
-  if (kc == 32 && nw == 4) return launch_ss<MT, NT, 32, 4>(a, B, s);
+  if (kc == 16 && nw == 4) return launch_ss<MT, NT, 16, 4>(a, B, s, geom);
+  if (kc == 16 && nw == 8) return launch_ss<MT, NT, 16, 8>(a, B, s, geom);
+  if (kc == 32 && nw == 4) return launch_ss<MT, NT, 32, 4>(a, B, s, geom);
 #endif
-  return launch_ss<MT, NT, SS_KC, SS_NW>(a, B, s);
+  return launch_ss<MT, NT, SS_KC, SS_NW>(a, B, s, geom);
 }
 
 bool skip_gemm_ok(const ConvArgs& a, int ks, int mode, int act, int B) {
@@ -591,19 +603,19 @@ bool skip_gemm_ok(const ConvArgs& a, int ks, int mode, int act, int B) {
          a.wpk && (ss_tile(a, mt, nt) || sg_tile(a, B, mt, nt));
 }
 
-hipError_t launch_skip_gemm(const ConvArgs& a, int B, hipStream_t s) {
+hipError_t launch_skip_gemm(const ConvArgs& a, int B, hipStream_t s, SkipGemmGeom* geom) {
   int mt, nt;
   if (ss_tile(a, mt, nt)) {
-    if (mt == 128) return launch_ss_tile<128, 128>(a, B, s);
-    if (nt == 256) return launch_ss_tile<64, 256>(a, B, s);
-    return launch_ss_tile<64, 128>(a, B, s);
+    if (mt == 128) return launch_ss_tile<128, 128>(a, B, s, geom);
+    if (nt == 256) return launch_ss_tile<64, 256>(a, B, s, geom);
+    return launch_ss_tile<64, 128>(a, B, s, geom);
   }
   if (!sg_tile(a, B, mt, nt)) return hipErrorInvalidValue;
-  if (mt == 64 && nt == 256) return launch_sg<64, 256>(a, B, s);
-  if (mt == 64 && nt == 128) return launch_sg<64, 128>(a, B, s);
-  if (mt == 64) return launch_sg<64, 64>(a, B, s);
-  if (nt == 64) return launch_sg<128, 64>(a, B, s);
-  return launch_sg<128, 128>(a, B, s);
+  if (mt == 64 && nt == 256) return launch_sg<64, 256>(a, B, s, geom);
+  if (mt == 64 && nt == 128) return launch_sg<64, 128>(a, B, s, geom);
+  if (mt == 64) return launch_sg<64, 64>(a, B, s, geom);
+  if (nt == 64) return launch_sg<128, 64>(a, B, s, geom);
+  return launch_sg<128, 128>(a, B, s, geom);
 }
 
 }  // namespace unet

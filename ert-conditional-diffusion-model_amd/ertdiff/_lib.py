@@ -56,6 +56,17 @@ class PackDesc(ctypes.Structure):
                 ("reserved", ctypes.c_int)]
 
 
+class RouteInfo(ctypes.Structure):
+    """ertd_route_info (include/ertdiff.h): the kernel an ertd_conv2d call dispatches."""
+    _fields_ = [("kernel", ctypes.c_int), ("ksplit", ctypes.c_int), ("items", ctypes.c_int),
+                ("grid", ctypes.c_int), ("gn_parts", ctypes.c_int)]
+
+
+# ERTD_ROUTE_* in value order
+ROUTE_KERNELS = ("direct", "conv_in", "conv_out", "up", "conv1x1", "skip_gemm", "skip_gemm_split",
+                 "f2", "f4", "f4s", "f4s_up", "bf16")
+
+
 SIGNATURES = {
     "ertd_version": (_I, []),
     "ertd_error_string": (ctypes.c_char_p, [_I]),
@@ -109,6 +120,7 @@ SIGNATURES = {
     "ertd_conv2d_run": (_I, [_VP, _I, _VP, _I, _I, _I, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _VP, _I,
                              _VP, _SZ, _VP]),
     "ertd_conv2d_gn_parts": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "ertd_conv2d_route_info": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(RouteInfo)]),
     "ertd_conv2d_gn": (_I, [_VP, _I, _VP, _I, _I, _I, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _VP,
                             _I, _VP, _SZ, _VP, _I, _VP]),
     "ertd_conv2d_run_gn": (_I, [_VP, _I, _VP, _I, _I, _I, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP, _VP, _I,

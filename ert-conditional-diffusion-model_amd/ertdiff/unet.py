@@ -16,6 +16,8 @@ param_dim) contract of sample_model (:107); ``sample_model`` dispatches to
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes
 import math
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -444,11 +446,12 @@ _ACTS = {"none": 0, "gn_silu": 1, "gn": 2}
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, mode: str = "same",
            act: str = "none", gn: Optional[torch.Tensor] = None, x2: Optional[torch.Tensor] = None,
            ebias: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
-           precision: str = "fp32") -> torch.Tensor:
+           precision: str = "fp32", out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One U-Net convolution on the HIP kernel: conv(act(cat(x, x2))) + bias
     (+ ebias[:, :, None, None]) (+ res); padding 1 for 3x3 (stride 2 for
     mode="down", nearest x2 upsample first for mode="up").  gn: (B, Cin, 2)
-    {scale, shift} as returned by group_norm_stats."""
+    {scale, shift} as returned by group_norm_stats.  out: the caller's
+    (B, Cout, Ho, Ho) contiguous float32 output (default: a new tensor)."""
     dev = _lib.require_device(x, weight, bias)
     x = _lib.f32c(x, "x")
     B, Ca, H, _ = x.shape
@@ -457,7 +460,11 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, mode: s
     if Cin != Ca + Cb:
         raise RuntimeError("ertdiff: weight in-channels != input channels")
     Ho = H // 2 if mode == "down" else (2 * H if mode == "up" else H)
-    out = torch.empty(B, Cout, Ho, Ho, dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty(B, Cout, Ho, Ho, dtype=torch.float32, device=dev)
+    elif (tuple(out.shape) != (B, Cout, Ho, Ho) or out.dtype != torch.float32 or out.device != dev
+          or not out.is_contiguous()):
+        raise RuntimeError("ertdiff: out must be a contiguous float32 (B, Cout, Ho, Ho) tensor on the device")
     prec = _PRECISIONS[precision]
     n = _lib.lib().ertd_conv2d_workspace_bytes(Cin, Cout, ks, prec, B, H, _MODES2D[mode])
     if n == 0:
@@ -474,6 +481,26 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, *, mode: s
             0 if eb is None else eb.shape[1], _lib.ptr(None if res is None else _lib.f32c(res, "res")),
             out.data_ptr(), prec, ws.data_ptr(), ws.numel(), _lib.stream_of(dev)), "conv2d")
     return out
+
+
+ConvRoute = collections.namedtuple("ConvRoute", "kernel ksplit items grid gn_parts")
+
+
+def conv2d_route(Ca: int, Cb: int, Cout: int, ks: int, B: int, H: int, *, mode: str = "same",
+                 act: str = "none", precision: str = "fp32", ebias: bool = False, res: bool = False,
+                 device=None) -> ConvRoute:
+    """The kernel conv2d dispatches for this geometry on `device` (default: the
+    current one) and its persistent launch (ertd_conv2d_route_info; nothing is
+    launched): kernel (one of _lib.ROUTE_KERNELS), ksplit, items, grid (0, 0 for
+    kernels that are not persistent) and gn_parts.  H: the input size."""
+    info = _lib.RouteInfo()
+    flags = (1 if ebias else 0) | (2 if res else 0)
+    ctx = torch.cuda.device(device) if device is not None else contextlib.nullcontext()
+    with ctx:
+        _lib.check(_lib.lib().ertd_conv2d_route_info(Ca, Cb, Cout, ks, _MODES2D[mode], _ACTS[act],
+                                                     _PRECISIONS[precision], flags, B, H,
+                                                     ctypes.byref(info)), "conv2d_route_info")
+    return ConvRoute(_lib.ROUTE_KERNELS[info.kernel], info.ksplit, info.items, info.grid, info.gn_parts)
 
 
 def group_norm_stats(x: torch.Tensor, groups: int, gamma: torch.Tensor, beta: torch.Tensor,

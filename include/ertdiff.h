@@ -478,6 +478,49 @@ int ertd_conv2d_run_gn(const float* x, int Ca, const float* x2, int Cb, int B, i
                        int Cout, int ks, int mode, const float* gn, int act, const float* ebias,
                        int eb_stride, const float* res, float* out, int precision, void* ws,
                        size_t ws_bytes, float* gn_parts, int gn_np, void* stream);
+/* ertd_conv2d_route_info: which kernel an ertd_conv2d call with this geometry
+ *   dispatches and how it is laid over the device -- a read-only query that
+ *   launches nothing, computed by the dispatch functions the launch itself
+ *   runs (so it holds for the device's CU count and the library's defaults).
+ *   has_ebias: bit 0 = the call has an ebias operand, bit 1 = a res operand
+ *   (operands some kernels do not take).  Returns ERTD_OK, or ERTD_EINVAL for
+ *   a geometry ertd_conv2d rejects.
+ *   kernel   ERTD_ROUTE_*;
+ *   ksplit   2: a Winograd layer's input channels run as two half-items, else 1;
+ *   items, grid   persistent kernels (the Winograd convs, the skip GEMMs): work
+ *            items of the launch and its workgroups; workgroup g runs items g,
+ *            g + grid, ... (in the F4S kernel's XCD-aware order where it takes
+ *            it), so with items > grid and items % grid != 0 neighbouring
+ *            workgroups run different numbers of items.  0, 0 otherwise;
+ *   gn_parts what ertd_conv2d_gn_parts returns for the call.
+ * Placement invariance (the persistent kernels' contract): a sample's output
+ *   bits depend on that sample's operands and on the route -- (kernel, ksplit,
+ *   tile), a function of the geometry and B -- and on nothing else: not on the
+ *   sample's position in the batch, hence not on the item, the round or the
+ *   workgroup that computes it, nor on how many items that workgroup runs.
+ *   Permuting the samples of a batch permutes the output bit for bit.  (The
+ *   skip GEMM's tile does not depend on B either: there a sample's bits do not
+ *   depend on the batch at all.)  */
+#define ERTD_ROUTE_DIRECT 0           /* implicit GEMM (1x1 / 3x3, any stride)      */
+#define ERTD_ROUTE_CONV_IN 1          /* Cin = 1 3x3                                */
+#define ERTD_ROUTE_CONV_OUT 2         /* Cout = 1 3x3                               */
+#define ERTD_ROUTE_UP 3               /* sub-pixel Upsample conv                    */
+#define ERTD_ROUTE_CONV1X1 4          /* 1x1, LDS-DMA                               */
+#define ERTD_ROUTE_SKIP_GEMM 5        /* 1x1 batched GEMM, fp32 MFMA                */
+#define ERTD_ROUTE_SKIP_GEMM_SPLIT 6  /* 1x1 batched GEMM, split-bf16 MFMA          */
+#define ERTD_ROUTE_F2 7               /* Winograd F(2x2,3x3)                        */
+#define ERTD_ROUTE_F4 8               /* Winograd F(4x4,3x3), weights in LDS        */
+#define ERTD_ROUTE_F4S 9              /* Winograd F(4x4,3x3), weights in registers  */
+#define ERTD_ROUTE_F4S_UP 10          /* ... on the nearest-x2 source (Upsample)    */
+#define ERTD_ROUTE_BF16 11            /* the bf16 / split-bf16 operand convs        */
+typedef struct ertd_route_info {
+  int kernel;
+  int ksplit;
+  int items, grid;
+  int gn_parts;
+} ertd_route_info;
+int ertd_conv2d_route_info(int Ca, int Cb, int Cout, int ks, int mode, int act, int precision,
+                           int has_ebias, int B, int H, ertd_route_info* out);
 int ertd_group_norm_stats(const float* x, int Ca, const float* x2, int Cb, int B, int HW,
                           int groups, const float* gamma, const float* beta, float* out,
                           void* stream);

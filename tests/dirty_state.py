@@ -18,6 +18,9 @@ buffer read before it is written.  The tools here take that luck away:
                        NaN, 0xFFFFFFFF counters, -1 integers), pattern bands;
   check_fences(...)    every band byte for byte intact, else the tensor's name
                        and the first changed offset;
+  sentinel_empty(...)  an fp32 output followed by 4096 words 0x7FC0DEAD in the
+                       same allocation (a work item too many writes there);
+  check_sentinel(...)  every one of those words intact;
   dirty_allocator()    for its duration torch.empty / torch.empty_like fill
                        every CUDA tensor they return with 0xFF bytes.
 
@@ -99,6 +102,50 @@ def poisoned_ws(nbytes: int, device="cpu", guard_bytes: int = GUARD_BYTES, name=
     """A workspace of exactly ``nbytes`` bytes (the value the entry's
     *_ws_bytes / *_workspace_bytes query returned), all 0xFF, fenced."""
     return fenced_empty((int(nbytes),), torch.uint8, device, guard_bytes, POISON_BYTE, name)
+
+
+SENTINEL_WORD = 0x7FC0DEAD   # a quiet fp32 NaN no arithmetic produces
+SENTINEL_WORDS = 4096
+
+
+class _Tail:
+    __slots__ = ("raw", "numel", "word", "name")
+
+    def __init__(self, raw, numel, word, name):
+        self.raw, self.numel, self.word, self.name = raw, numel, word, name
+
+
+def sentinel_empty(shape, device="cpu", words: int = SENTINEL_WORDS, word: int = SENTINEL_WORD, name=None):
+    """An fp32 output whose last element is followed, in the same allocation,
+    by ``words`` 32-bit words ``word``: an entry that runs one work item too
+    many writes there.  Interior prefilled with 0xFF bytes (NaN)."""
+    if isinstance(shape, int):
+        shape = (shape,)
+    shape = tuple(int(s) for s in shape)
+    n = 1
+    for s in shape:
+        n *= s
+    if not 0 <= word < 2 ** 31:
+        raise ValueError("word must fit a non-negative int32")
+    raw = torch.full((n + int(words),), -1, dtype=torch.int32, device=torch.device(device))
+    raw[n:] = word
+    view = raw[:n].view(torch.float32).view(shape)
+    view._tail = _Tail(raw, n, word, name or "tensor")
+    return view
+
+
+def check_sentinel(*tensors):
+    """Assert that every word behind each sentinel_empty tensor still holds its value."""
+    for t in tensors:
+        f = getattr(t, "_tail", None)
+        if f is None:
+            raise TypeError("check_sentinel: not a tensor made by sentinel_empty")
+        bad = (f.raw[f.numel:] != f.word).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise AssertionError(f"{f.name}: write past the end, first changed word {i} behind a "
+                                 f"{f.numel}-element tensor (0x{int(f.raw[f.numel + i]) & 0xFFFFFFFF:08x}, "
+                                 f"sentinel 0x{f.word:08x}), {bad.numel()} words changed")
 
 
 def _first_changed(band: torch.Tensor, byte: int):

@@ -166,3 +166,17 @@ def test_dirty_allocator(monkeypatch):
         with DS.dirty_allocator(devices=("cpu",)):
             1 / 0
     assert torch.empty is real_empty and torch.empty_like is real_like
+
+
+def test_sentinel_tail_catches_one_word_past_the_end():
+    out = DS.sentinel_empty((3, 5), name="out")
+    assert out.shape == (3, 5) and out.dtype == torch.float32 and bool(torch.isnan(out).all())
+    tail = out._tail.raw[out.numel():]
+    assert tail.numel() == DS.SENTINEL_WORDS and bool((tail == DS.SENTINEL_WORD).all())
+    out.fill_(1.0)                       # writes inside the tensor leave the tail alone
+    DS.check_sentinel(out)
+    out._tail.raw[out.numel() + 7] = 0   # one word behind the last element
+    with pytest.raises(AssertionError, match="out: write past the end, first changed word 7"):
+        DS.check_sentinel(out)
+    with pytest.raises(TypeError):
+        DS.check_sentinel(torch.zeros(2))

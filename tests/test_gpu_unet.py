@@ -433,3 +433,111 @@ def test_unet_bf16x3_forward(name, B, L, ts, cuda_dev):
     e32 = RN.rel_l2(out, ref32)
     record_error(f"unet_forward_{name}_bf16x3_vs_fp32spec", e32)
     assert e32 < 1e-4, e32
+
+
+# ---- the headline network at a batch people use: not a multiple of 16 ----------
+# The reference evaluates 50 realisations per condition.  At B = 50 on 256 CUs
+# the persistent F(4x4) convs of U2 run 800 items at 64x64 (workgroups of 4 and
+# 3), 400 at 32x32 (2 and 1: the consumer-side GroupNorm finalize, whose LDS
+# table is sized for the larger count) and 400 K-split half-items at 16x16.
+# The batch is chosen from the route query so the same walk is hit on any part.
+def _u2_ragged_batch(dev):
+    from ragged_route import B_MAX, Shape, is_ragged, rounds, route
+    levels = [Shape(64, 0, 64, 64, act="gn_silu", res=True), Shape(128, 0, 128, 32, act="gn_silu", res=True),
+              Shape(256, 0, 256, 16, act="gn_silu", res=True)]
+    for B in range(50, B_MAX + 1):
+        r = [route(s, B, dev) for s in levels]
+        if (is_ragged(r[0], "f4s", 1) and is_ragged(r[1], "f4s", 1) and rounds(r[1]) == 2 and
+                is_ragged(r[2], "f4s", 2)):
+            return B, r
+    pytest.skip("no 50 <= B <= 192 runs U2's 64x64 and 32x32 levels raggedly (32x32 in two rounds) and its "
+                "16x16 level K-split and raggedly on this device")
+
+
+def _ragged_members(B, r):
+    """First and last member, the two on each side of the 32x32 level's round
+    boundary, two of the 64x64 level's last round."""
+    b32 = r[1].grid // (r[1].items // B)                    # first member of the 32x32 level's second round
+    last = (r[0].items - 1) // r[0].grid * r[0].grid        # first item of the 64x64 level's last round
+    b64 = -(-last // (r[0].items // B))                     # first member wholly inside it
+    assert 0 < b32 < B and b64 < B, (b32, b64)
+    idx = {0, B - 1, b32 - 1, b32, min(b64, B - 1), min(b64 + 1, B - 1)}
+    for b in (b32 + 1, b32 - 2, b32 + 2, b32 - 3):   # the last round may hold B - 1 alone: six members all the same
+        if len(idx) < 6 and 0 <= b < B:
+            idx.add(b)
+    return sorted(idx)
+
+
+@pytest.fixture(scope="module")
+def u2_ragged(cuda_dev):
+    B, r = _u2_ragged_batch(cuda_dev)
+    cfg = U.CONFIGS["U2"]
+    W = U.init_weights(cfg, 21, affine="random")
+    return B, r, cfg, W, _model_from_spec("U2", W, cuda_dev)
+
+
+def test_unet_u2_forward_ragged_batch(u2_ragged, cuda_dev):
+    """U2, fp32, L = 257, random GroupNorm affine at the smallest B >= 50 at which
+    every level's ResBlock convs walk items that do not divide the grid: six
+    members against the spec, each alone <= 1e-5, and the whole batch bit for
+    bit equal to itself with the members rolled by B // 2 + 1 (same B, so the
+    same routes; every member on other items, rounds and workgroups)."""
+    from ragged_route import assert_ragged, rounds
+    B, r, cfg, W, m = u2_ragged
+    assert_ragged(r[0], "f4s", 1)
+    assert_ragged(r[1], "f4s", 1)
+    assert rounds(r[1]) == 2, r[1]
+    assert_ragged(r[2], "f4s", 2)
+    L = 257
+    x = torch.from_numpy(synth_normal((B, cfg.param_dim), 171))
+    cond = torch.from_numpy(synth_uniform((B, 14, L), 172))
+    t = torch.arange(B) * 997 % 1000
+    idx = _ragged_members(B, r)
+    k = B // 2 + 1
+    with torch.no_grad():
+        out = m(x.to(cuda_dev), t.to(cuda_dev), cond.to(cuda_dev))
+        rolled = m(torch.roll(x, k, 0).to(cuda_dev), torch.roll(t, k, 0).to(cuda_dev),
+                   torch.roll(cond, k, 0).to(cuda_dev))
+        ref = U.forward(x[idx], t[idx], cond[idx], W, cfg)
+    got = out.cpu()
+    for j, b in enumerate(idx):
+        err = RN.rel_l2(got[b].double().numpy(), ref[j].double().numpy())
+        record_error(f"unet_forward_U2_ragged_B{B}_member{b}", err)
+        assert err < 1e-5, (b, err)
+    back = torch.roll(rolled, -k, 0)
+    if not torch.equal(back, out):
+        bad = (back != out).flatten(1).any(1).nonzero().flatten().tolist()
+        raise AssertionError(f"{len(bad)} of {B} members change bits with their position in the batch: {bad[:8]}")
+
+
+def test_unet_plan_ragged_batch(u2_ragged, cuda_dev):
+    """Three sampler steps of the same model and batch through the captured step
+    graph and through the direct path: bit for bit equal, and the six members
+    within SAMPLER_TOL of the spec's 3-step chain."""
+    from ragged_route import assert_ragged, rounds
+    B, r, cfg, W, m = u2_ragged
+    assert_ragged(r[0], "f4s", 1)
+    assert_ragged(r[1], "f4s", 1)
+    assert rounds(r[1]) == 2, r[1]
+    assert_ragged(r[2], "f4s", 2)
+    L, T, P = 257, 3, m.param_dim
+    cond = torch.from_numpy(synth_uniform((B, 14, L), 173))
+    noise = torch.from_numpy(synth_normal((T, B, P), 174))
+    sched = ertdiff.get_diffusion_schedule(T, device=cuda_dev)
+    cd, nd = cond.to(cuda_dev), noise.to(cuda_dev)
+    a = ertdiff.sample_model(m, cd, T, *sched, P, cuda_dev, noise=nd)
+    plan = ertdiff.UNetSamplerPlan(m, cd, T, *sched, noise=nd)
+    plan.x.copy_(nd[0])
+    plan.launch()
+    torch.cuda.synchronize()
+    same = torch.equal(plan.x, a)
+    plan.close()
+    assert same
+    idx = _ragged_members(B, r)
+    with torch.no_grad():
+        ref = U.sample(cond[idx], W, cfg, T, noise[:, idx])
+    got = a.cpu()
+    for j, b in enumerate(idx):
+        err = RN.rel_l2(got[b].double().numpy(), ref[j].double().numpy())
+        record_error(f"unet_chain3_U2_ragged_B{B}_member{b}", err)
+        assert err < SAMPLER_TOL, (b, err)

@@ -237,11 +237,17 @@ def test_conv2d_1x1_skip_kernel(B, cuda_dev):
 
 
 def test_conv2d_wino4_16x16_two_sample_blocks(cuda_dev):
-    """Winograd F(4x4,3x3) at 16x16 (taken only when its tile items fill the
-    CUs without a K split: B=128, Cout=256 -> 256 items): a 32-tile block holds
-    two samples (per-lane sample offset, GroupNorm row and epilogue base), with
-    the embedding and residual epilogue."""
+    """The 16x16 level at B = 128, 256 -> 256 channels, with the embedding and
+    residual epilogue.  Cin % 8 == 0 and 64 co x 16 tile items that fill the CUs
+    (512 on 256 CUs) send this shape to the register-weight F(4x4) kernel
+    (conv_wino4s_kernel, route "f4s"), whose 16-tile block holds one sample --
+    not to conv_wino4_kernel, whose two-sample 32-tile blocks at 16x16 need
+    Cin % 8 == 4 (test_gpu_conv_ragged.py, cases j).  The kernel is asserted
+    from the route query; the name is kept for the error record's history."""
+    from ertdiff.unet import conv2d_route
     B, C, H = 128, 256, 16
+    r = conv2d_route(C, 0, C, 3, B, H, act="gn_silu", ebias=True, res=True, device=cuda_dev)
+    assert r.kernel == "f4s" and r.items == B * (C // 64), r
     x, w, b = _rand((B, C, H, H), 40), _rand((C, C, 3, 3), 41, 1.0 / np.sqrt(9 * C)), _rand((C,), 42, 0.1)
     gn = torch.stack([_rand((B, C), 43, 0.3) + 1.0, _rand((B, C), 44, 0.2)], -1)
     eb, res = _rand((B, C), 45), _rand((B, C, H, H), 46)

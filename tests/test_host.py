@@ -312,3 +312,47 @@ def test_unet_spec_random_affine_init():
             assert not torch.equal(a[k], r[k]) and r[k].unique().numel() == r[k].numel(), k
         else:
             assert torch.equal(a[k], r[k]), k
+
+
+def test_conv2d_route_query_host():
+    """ertd_conv2d_route_info launches nothing, so it answers without a GPU (the
+    CU count then defaults): the kernels whose choice does not depend on the
+    CU count, persistent geometry only for persistent kernels, gn_parts that of
+    ertd_conv2d_gn_parts, and rejected geometries."""
+    import ctypes
+    from ertdiff.unet import conv2d_route
+    lib = _lib.load()
+    assert conv2d_route(1, 0, 64, 3, 2, 64).kernel == "conv_in"
+    assert conv2d_route(1, 0, 64, 3, 2, 64, res=True).kernel == "direct"      # conv_in takes no residual
+    assert conv2d_route(64, 0, 1, 3, 2, 64, act="gn_silu").kernel == "conv_out"
+    assert conv2d_route(64, 0, 64, 3, 2, 64, mode="down").kernel == "direct"
+    assert conv2d_route(20, 0, 40, 3, 2, 16, mode="up").kernel == "up"
+    assert conv2d_route(64, 0, 96, 3, 2, 32, act="gn_silu").kernel == "direct"   # Cout % 64 != 0
+    assert conv2d_route(64, 0, 64, 3, 2, 32, act="gn_silu", precision="bf16").kernel == "bf16"
+    assert conv2d_route(64, 0, 1, 3, 2, 32, act="gn_silu", precision="bf16x3").kernel == "conv_out"
+    assert conv2d_route(256, 0, 768, 1, 2, 16, act="gn").kernel == "direct"      # attention qkv
+    for r in (conv2d_route(1, 0, 64, 3, 2, 64), conv2d_route(64, 0, 64, 3, 2, 64, mode="down"),
+              conv2d_route(64, 0, 64, 3, 2, 32, precision="bf16")):
+        assert (r.items, r.grid, r.ksplit) == (0, 0, 1), r
+    # the persistent kernels: 64 co x 16 tile items of the register-weight F(4x4) kernel, skip GEMM tiles
+    r = conv2d_route(64, 0, 64, 3, 1, 64, act="gn_silu", ebias=True, res=True)
+    assert (r.kernel, r.ksplit, r.items, r.grid) == ("f4s", 1, 16, 16), r
+    assert r.gn_parts == lib.ertd_conv2d_gn_parts(64, 0, 64, 3, 0, 1, 0, 1, 64) == 16
+    r = conv2d_route(128, 64, 64, 1, 1, 64)
+    assert (r.kernel, r.items, r.grid, r.gn_parts) == ("skip_gemm_split", 16, 16, 0), r   # 64 x 256 tiles
+    assert conv2d_route(128, 64, 64, 1, 2, 64, ebias=True).kernel == "direct"   # no 1x1 kernel but it takes an ebias
+    for B in (1, 7, 50, 64, 130):
+        for sh in ((64, 0, 64, 3, 64), (128, 0, 128, 3, 32), (256, 0, 256, 3, 16), (12, 0, 256, 3, 16),
+                   (256, 256, 256, 1, 16)):
+            r = conv2d_route(*sh[:4], B, sh[4], act="gn_silu" if sh[3] == 3 else "none")
+            assert r.kernel in _lib.ROUTE_KERNELS and r.ksplit in (1, 2)
+            persistent = r.kernel in ("f2", "f4", "f4s", "f4s_up", "skip_gemm", "skip_gemm_split")
+            assert (0 < r.grid <= r.items) if persistent else (r.items, r.grid) == (0, 0), r
+            assert r.gn_parts == lib.ertd_conv2d_gn_parts(sh[0], sh[1], sh[2], sh[3], 0, 1 if sh[3] == 3 else 0,
+                                                          0, B, sh[4])
+    info = _lib.RouteInfo()
+    bad = [(0, 0, 64, 3, 0, 0, 0, 0, 2, 64), (64, 0, 64, 5, 0, 0, 0, 0, 2, 64), (64, 0, 64, 1, 1, 0, 0, 0, 2, 64),
+           (64, 0, 64, 3, 0, 3, 0, 0, 2, 64), (64, 0, 64, 3, 0, 0, 9, 0, 2, 64), (64, 0, 64, 3, 0, 0, 0, 0, 0, 64)]
+    for a in bad:
+        assert lib.ertd_conv2d_route_info(*a, ctypes.byref(info)) == _lib.ERTD_EINVAL, a
+    assert lib.ertd_conv2d_route_info(64, 0, 64, 3, 0, 0, 0, 0, 2, 64, None) == _lib.ERTD_EINVAL
