@@ -16,7 +16,20 @@
 //   * 4 producer waves, each two channels of the chunk (lane = channel bit 5,
 //     column half bit 4, tile bits 0-3), do GroupNorm + SiLU + B^T d B exactly
 //     as conv_wino4_kernel's producers (the half exchange is v_permlane16_swap:
-//     the halves are 16 lanes apart here);
+//     the halves are 16 lanes apart here); at 16x16 and 32x32 (WINO4S_HALO) a
+//     lane loads and activates only its tile's 4 own rows (window rows 1-4)
+//     and takes window rows 0 and 5 -- the own rows 4 and 1 of the tiles above
+//     and below, 4 / 8 lanes away in its 16-lane row -- by DPP row shifts: 4
+//     (16x16) or 5 (32x32: one extra row where the neighbour tile belongs to
+//     another item) loads and activations per slot instead of 6.  A row taken
+//     from a neighbour is the row this lane would have computed (same sample,
+//     channel, GroupNorm pair, columns, same instruction sequence), so for
+//     finite inputs every output bit is what the six-row path gives.  The one
+//     difference: a padded window row at 16x16 is now an exact 0 (the DPP's
+//     out-of-row value, bound_ctrl) times the 0 pad factor, where the six-row
+//     path re-reads a clamped row, activates it and multiplies by 0 -- NaN if
+//     that row holds a non-finite value (as the 32x32 extra row and the 64x64
+//     path still do);
 //   * XS = 1: 512 threads, 256 VGPRs per wave (2 waves per SIMD), 36 KB of LDS;
 //   * XS = 2 (the default): each co block's 36 xi are split over two MFMA
 //     waves (8 MFMA waves, 768 threads, 163 VGPRs, 36 + 64 KB of LDS); the
@@ -70,6 +83,9 @@ constexpr int GNC_TAB = 4096;                 //   table entries (item x channel
 #ifndef WINO4S_PACK
 #define WINO4S_PACK 1                         // producer stage on packed fp32 pairs
 #endif
+#ifndef WINO4S_HALO
+#define WINO4S_HALO 1                         // 16x16 / 32x32 producers: own rows once, halo rows by DPP (needs WINO4S_PACK)
+#endif
 #ifndef WINO4S_RPF
 #define WINO4S_RPF 0                          // residual L2 prefetch this many chunks before the epilogue
                                               // (0: none; 2: 250.2 vs 252.2 steps/s U2 B=64, same box)
@@ -115,6 +131,22 @@ __device__ __forceinline__ void bt6p(const f32x2 (&d)[6], f32x2 (&o)[6]) {
   o[3] = pfma(e, 2.f, c);
   o[4] = pfma(e, -0.5f, c);
   o[5] = pfma(c, 1.5f, pfma(d[3], -2.f, d[1] + d[5]));
+}
+// v shifted by N lanes inside each row of 16 lanes (DPP row_shr: lane l takes
+// lane l - N, row_shl: lane l + N); a lane whose source lies outside the row
+// gets 0 (bound_ctrl), never stale register contents ...
+template <int N, bool SHL>
+__device__ __forceinline__ f32x2 row_shift0(f32x2 v) {
+  constexpr int ctrl = (SHL ? 0x100 : 0x110) + N;
+  return f32x2{__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.x), ctrl, 0xf, 0xf, true)),
+               __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v.y), ctrl, 0xf, 0xf, true))};
+}
+// ... or keeps its value of `old`
+template <int N, bool SHL>
+__device__ __forceinline__ f32x2 row_shift_keep(f32x2 old, f32x2 v) {
+  constexpr int ctrl = (SHL ? 0x100 : 0x110) + N;
+  return f32x2{__int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old.x), __float_as_int(v.x), ctrl, 0xf, 0xf, false)),
+               __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old.y), __float_as_int(v.y), ctrl, 0xf, 0xf, false))};
 }
 __device__ __forceinline__ void at6(const f32x2 (&m)[6], f32x2 (&y)[4]) {
   const f32x2 s = m[1] + m[2], d = m[1] - m[2];
@@ -274,12 +306,21 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
     // the outer window column from the neighbouring tile's other half (16 lanes apart)
     const int nbaddr = (lane + 15 - 30 * h) * 4;
     const unsigned choff = (unsigned)(chb * HWS * 4);
-    float2 raw[NRS][6];
+    // HALO (16x16 and 32x32, stride 1): an item is 4 / 2 whole tile rows of one
+    // sample and tile t + TPR sits in the same 16-lane row of the wave, so
+    // window rows 0 and 5 of a tile are the activated own rows 4 and 1 (window
+    // rows 1-4 are a tile's own) of lanes t - TPR and t + TPR: a lane loads and
+    // activates its own rows once and takes the halo rows by DPP.  At 32x32
+    // the item's upper tile row has no lane above and the lower none below:
+    // every lane runs one extra row, window row 0 (t < 8) or 5 (t >= 8).
+    constexpr bool HALO = WINO4S_HALO && WINO4S_PACK && !UP && TPR <= 8;
+    constexpr int NWR = HALO ? (TPR == 8 ? 5 : 4) : 6;   // rows loaded per slot
+    float2 raw[NRS][NWR];
     float2 gnv[NRS];
     int gch[NRS];
     f32x4 pad[NRS];
     int cur_g = 0, cur_k = 0, cur_b = 0, cur_il = 0, cur_k0 = 0;
-    unsigned roff[6];   // per window row (UP: per distinct source row, 4)
+    unsigned roff[NWR];   // per window row (UP: per distinct source row, 4; HALO: rows 1-4, the extra row)
     f32x4 cur_pad;
     auto set_item = [&](int il) {
       const Item itm = wk.at(il);
@@ -293,6 +334,13 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         for (int r = 0; r < 4; ++r) {
           const int sy = 2 * ty - 1 + r;
           roff[r] = (unsigned)(((sy >= 0 && sy < WS ? sy : 2 * ty) * WS + 2 * tx + h) * 4) + choff;
+        }
+      } else if constexpr (HALO) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) roff[r] = (unsigned)(((4 * ty + r) * WO + 4 * tx + 2 * h) * 4) + choff;
+        if constexpr (TPR == 8) {
+          const int iy = t < 8 ? 4 * ty - 1 : 4 * ty + 4;
+          roff[4] = (unsigned)(((iy >= 0 && iy < WO ? iy : 4 * ty) * WO + 4 * tx + 2 * h) * 4) + choff;
         }
       } else {
 #pragma unroll
@@ -326,7 +374,7 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         }
       } else {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) {
+        for (int r = 0; r < NWR; ++r) {
           const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)roff[r], 0, 0);
           raw[set][r] = make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
         }
@@ -353,19 +401,36 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
     float actn[2][6];
     auto act_stage = [&](const int set, const int ab) {
       if constexpr (GNC) gnv[set] = gtab[gch[set]];
-      f32x2 m[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        m[r] = f32x2{raw[set][r].x, raw[set][r].y};
+      auto activate = [&](const float2 rw) {
+        f32x2 v = f32x2{rw.x, rw.y};
         if constexpr (ACT != ACT_NONE) {
-          m[r] = __builtin_elementwise_fma(m[r], f32x2{gnv[set].x, gnv[set].x}, f32x2{gnv[set].y, gnv[set].y});
+          v = __builtin_elementwise_fma(v, f32x2{gnv[set].x, gnv[set].x}, f32x2{gnv[set].y, gnv[set].y});
           if constexpr (ACT == ACT_GN_SILU) {
             // __expf(-y) = exp2(y * -log2 e): the same v_mul + v_exp as the scalar code
-            f32x2 e = m[r] * f32x2{-1.44269504088896340736f, -1.44269504088896340736f};
+            f32x2 e = v * f32x2{-1.44269504088896340736f, -1.44269504088896340736f};
             e = f32x2{__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)} + f32x2{1.0f, 1.0f};
-            m[r] = m[r] * f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
+            v = v * f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
           }
         }
+        return v;
+      };
+      f32x2 m[6];
+      if constexpr (HALO) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) m[1 + r] = activate(raw[set][r]);
+        if constexpr (TPR == 8) {
+          // the extra row where the neighbour tile lies outside the item
+          const f32x2 x = activate(raw[set][4]);
+          m[0] = row_shift_keep<TPR, false>(x, m[4]);
+          m[5] = row_shift_keep<TPR, true>(x, m[1]);
+        } else {
+          // the sample's top and bottom tile rows: 0, times pad = 0 below
+          m[0] = row_shift0<TPR, false>(m[4]);
+          m[5] = row_shift0<TPR, true>(m[1]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) m[r] = activate(raw[set][r]);
       }
       m[0] = m[0] * f32x2{pad[set].x, pad[set].x};
       m[5] = m[5] * f32x2{pad[set].y, pad[set].y};
