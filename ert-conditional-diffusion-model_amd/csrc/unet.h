@@ -130,6 +130,8 @@ struct WinoRoute {
   bool fold_ok = false;   // the kernel takes ConvArgs::fold (diagnostic builds)
   int fold_target = 0;    // F4S / F4S_UP: items per sample = the fold's arrivals (GnFold::target)
   int pack_kind = ERTD_PACK_DIRECT;   // the weight packing the launch reads (ERTD_PACK_*)
+  bool up_points = false; // ERTD_PACK_WINO4 in the Upsample point set (F4S_UP: the kernel's
+                          // transforms and the packing's G are chosen together, here)
 };
 // mode / act as launch_conv; Wo = the OUTPUT width; have_*_pack: the F(2x2) /
 // F(4x4) packing exists (ConvArgs::wpk_wino / wpk_wino4); cus = device_cu_count()
@@ -412,8 +414,9 @@ hipError_t launch_conv_wino4s(int act, const ConvArgs& a, hipStream_t s, const W
 // multiple of 8, F(4x4) of 4, Cout of 64
 size_t conv_packed_floats_wino(int cin, int cout);
 size_t conv_packed_floats_wino4(int cin, int cout);
+// up: the Upsample point set's G, for a layer whose route has WinoRoute::up_points
 hipError_t launch_pack_conv_wino4(const float* w, int cin, int cout, float* dst, hipStream_t s,
-                                  bool flipT = false);
+                                  bool flipT = false, bool up = false);
 // schedule knobs of the F(4x4) register-weight kernel that the route and its
 // launcher both read (unet_conv_wino.hip)
 int wino4s_xs();

@@ -1065,7 +1065,8 @@ int conv2d_impl(const float* x, int Ca, const float* x2, int Cb, int B, int H, c
   ConvArgs a = conv2d_args(x, Ca, x2, Cb, H, bias, Cout, ks, mode, gn, ebias, eb_stride, res, out, precision,
                            pk, need, route);
   if (wino && pack &&
-      (e = wino4 ? launch_pack_conv_wino4(w, Cin, Cout, const_cast<float*>(a.wpk_wino4), s)
+      (e = wino4 ? launch_pack_conv_wino4(w, Cin, Cout, const_cast<float*>(a.wpk_wino4), s, false,
+                                          route.up_points)
                  : launch_pack_conv_wino(w, Cin, Cout, const_cast<float*>(a.wpk_wino), s)) != hipSuccess)
     return (int)e;
   if (gnp) {
@@ -1227,9 +1228,12 @@ int input_grad_impl(const float* dy, int B, int H, const float* w, int Cout, int
   return ERTD_OK;
 }
 
-void fill_desc(ertd_pack_desc* d, const float* w, float* dst, int cin, int cout, int ks, int kind, int flip) {
+void fill_desc(ertd_pack_desc* d, const float* w, float* dst, int cin, int cout, int ks, const WinoRoute& r,
+               int flip) {
+  const int kind = r.pack_kind;
   *d = ertd_pack_desc{};
   d->w = w; d->dst = dst; d->cin = cin; d->cout = cout; d->ks = ks; d->kind = kind; d->flip = flip;
+  d->reserved = r.up_points ? 1 : 0;   // ERTD_PACK_WINO4: the Upsample point set's G
   switch (kind) {
     case ERTD_PACK_DIRECT:
       d->total = (long long)conv_packed_floats(cin, cout, ks);
@@ -1269,7 +1273,7 @@ int ertd_conv_input_grad_pack_desc(int Cin, int Cout, int B, int H, int ks, int 
                                    void* ws, ertd_pack_desc* out) {
   if (!w || !ws || !out || ertd_conv_input_grad_ws_bytes(Cin, Cout, B, H, ks, mode) == 0)
     return ERTD_EINVAL;
-  fill_desc(out, w, (float*)ws, Cout, Cin, ks, input_grad_route(Cin, Cout, B, H, ks, mode).pack_kind, 1);
+  fill_desc(out, w, (float*)ws, Cout, Cin, ks, input_grad_route(Cin, Cout, B, H, ks, mode), 1);
   return ERTD_OK;
 }
 
@@ -1285,7 +1289,7 @@ int ertd_conv2d_pack_desc(int Cin, int Ca, int Cout, int ks, int mode, int preci
   const WinoRoute route = conv2d_route(Cin, Ca, Cout, ks, mode, ACT_NONE, precision, B, H);
   if (route.kernel != WinoRoute::NONE)   // the Winograd packings lie behind the direct one
     pk += a64(std::max(conv_packed_floats(Cin, Cout, ks), conv_packed_floats_up(Cin, Cout)));
-  fill_desc(out, w, pk, Cin, Cout, ks, route.pack_kind, 0);
+  fill_desc(out, w, pk, Cin, Cout, ks, route, 0);
   return ERTD_OK;
 }
 
@@ -1447,7 +1451,9 @@ int ertd_unet_pack(const ertd_unet_config* c, const float* const* params, const 
         e = launch_pack_conv_wino(src, p.shape[1], p.shape[0], packed + itw->second, s);
       const auto itw4 = L.offw4.find(p.name);
       if (e == hipSuccess && itw4 != L.offw4.end())
-        e = launch_pack_conv_wino4(src, p.shape[1], p.shape[0], packed + itw4->second, s);
+        // (an Upsample conv's F(4x4) packing is read by WinoRoute::F4S_UP only)
+        e = launch_pack_conv_wino4(src, p.shape[1], p.shape[0], packed + itw4->second, s, false,
+                                   ends_with(p.name, ".upsample.weight"));
     } else if (p.shape.size() == 2) {
       e = launch_transpose(src, p.shape[0], p.shape[1], packed + L.off.at(p.name), p.shape[0], s);
     } else {

@@ -730,6 +730,7 @@ WinoRoute wino_route(int mode, int act, int Cin, int Ca, int Cout, int Wo, int B
   r.fold_ok = s && !split;   // every MFMA wave of an unsplit item arrives once
   r.fold_target = s ? t4 / 16 * ncog : 0;
   r.pack_kind = f2 ? ERTD_PACK_WINO : ERTD_PACK_WINO4;
+  r.up_points = r.kernel == WinoRoute::F4S_UP;
   return r;
 }
 

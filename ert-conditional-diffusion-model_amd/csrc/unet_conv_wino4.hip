@@ -89,6 +89,14 @@ constexpr double GD[6][3] = {{1.0, 0.0, 0.0},
                              {-16.0 / 15, -8.0 / 15, -4.0 / 15},
                              {1.0 / 15, -2.0 / 15, 4.0 / 15},
                              {0.0, 0.0, 1.0}};
+// G of the Upsample conv's points {0, 1, 1/2, -1/2, -1, inf} (unet_conv_wino4s.hip,
+// bt6u; the same table as pack_wino4_tile's)
+constexpr double GD_UP[6][3] = {{1.0, 0.0, 0.0},
+                                {2.0 / 3, 2.0 / 3, 2.0 / 3},
+                                {-8.0 / 3, -4.0 / 3, -2.0 / 3},
+                                {-8.0 / 3, 4.0 / 3, -2.0 / 3},
+                                {2.0 / 3, -2.0 / 3, 2.0 / 3},
+                                {0.0, 0.0, 1.0}};
 
 __device__ __forceinline__ f32x2 fmac(f32x2 x, float c, f32x2 s) {
   return __builtin_elementwise_fma(x, f32x2{c, c}, s);
@@ -628,9 +636,10 @@ __global__ __launch_bounds__(WT) void conv_wino4_kernel(ConvArgs a, int nitems, 
 // (float64, rounded once): the A-operand fragments of v_mfma_f32_16x16x4_f32,
 // lane l = 16 k + c16 -> co = 16 cb + c16, channel k of the chunk
 __global__ void pack_wino4_kernel(const float* __restrict__ w, int cin, int cout, int nchunk,
-                                  size_t total, float* __restrict__ dst, bool flipT) {
+                                  size_t total, float* __restrict__ dst, bool flipT, bool up) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
+  const double (&GD)[6][3] = up ? GD_UP : unet::GD;
   const int e = (int)(i & 1);
   const int c16 = (int)((i >> 1) & 15);
   const int kk = (int)((i >> 5) & 3);
@@ -724,11 +733,11 @@ size_t conv_packed_floats_wino4(int cin, int cout) {
 }
 
 hipError_t launch_pack_conv_wino4(const float* w, int cin, int cout, float* dst, hipStream_t s,
-                                  bool flipT) {
+                                  bool flipT, bool up) {
   const size_t total = conv_packed_floats_wino4(cin, cout);
   if (!total) return hipErrorInvalidValue;
   pack_wino4_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(w, cin, cout, cin / WKC, total, dst,
-                                                                     flipT);
+                                                                     flipT, up);
   return hipGetLastError();
 }
 

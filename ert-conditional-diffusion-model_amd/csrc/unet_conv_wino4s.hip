@@ -132,6 +132,46 @@ __device__ __forceinline__ void bt6p(const f32x2 (&d)[6], f32x2 (&o)[6]) {
   o[4] = pfma(e, -0.5f, c);
   o[5] = pfma(c, 1.5f, pfma(d[3], -2.f, d[1] + d[5]));
 }
+// The Upsample conv's transforms: the points {0, 1, 1/2, -1/2, -1, inf} in
+// this index order (unet_pack.h: GD_UP is their G).  Window rows (columns) 1, 2
+// and 3, 4 of a nearest-x2 image are one source row (column) each, and row 4
+// of B^T -- the point -1, [0 .25 -.25 -1 1 0] -- is 0 on every (a, b, b, c, c, d):
+// row 4 and column 4 of V = B^T d B vanish for every tile, 11 of the 36 xi.
+//   B^T = [1  0   -5    0    4 0]     A^T = [1 1 1     1     1 0]
+//         [0 -.25 -.25  1    1 0]           [0 1 .5   -.5   -1 0]
+//         [0 -.5  -1    .5   1 0]           [0 1 .25   .25   1 0]
+//         [0  .5  -1   -.5   1 0]           [0 1 .125 -.125 -1 1]
+//         [0  .25 -.25 -1    1 0]
+//         [0  .25  0  -1.25  0 1]
+// DEAD4: o[4] is not computed (0): the xi-split kernel never reads it
+template <bool DEAD4>
+__device__ __forceinline__ void bt6u(const float (&d)[6], float (&o)[6]) {
+  const float c = d[4] - d[2], e = d[3] - d[1];
+  o[0] = __builtin_fmaf(4.f, d[4], __builtin_fmaf(-5.f, d[2], d[0]));
+  o[1] = __builtin_fmaf(-0.25f, d[1] + d[2], d[3] + d[4]);
+  o[2] = __builtin_fmaf(0.5f, e, c);
+  o[3] = __builtin_fmaf(-0.5f, e, c);
+  o[4] = DEAD4 ? 0.f : __builtin_fmaf(0.25f, d[1] - d[2], d[4] - d[3]);
+  o[5] = __builtin_fmaf(-1.25f, d[3], __builtin_fmaf(0.25f, d[1], d[5]));
+}
+template <bool DEAD4>
+__device__ __forceinline__ void bt6pu(const f32x2 (&d)[6], f32x2 (&o)[6]) {
+  const f32x2 c = d[4] - d[2], e = d[3] - d[1];
+  o[0] = pfma(d[4], 4.f, pfma(d[2], -5.f, d[0]));
+  o[1] = pfma(d[1] + d[2], -0.25f, d[3] + d[4]);
+  o[2] = pfma(e, 0.5f, c);
+  o[3] = pfma(e, -0.5f, c);
+  o[4] = DEAD4 ? f32x2{0.f, 0.f} : pfma(d[1] - d[2], 0.25f, d[4] - d[3]);
+  o[5] = pfma(d[3], -1.25f, pfma(d[1], 0.25f, d[5]));
+}
+// A^T m without m[4]: M of a dead xi is a sum of exact zeros
+__device__ __forceinline__ void at6u(const f32x2 (&m)[6], f32x2 (&y)[4]) {
+  const f32x2 s = m[2] + m[3], d = m[2] - m[3];
+  y[0] = (m[0] + m[1]) + s;
+  y[1] = fmac(d, 0.5f, m[1]);
+  y[2] = fmac(s, 0.25f, m[1]);
+  y[3] = fmac(d, 0.125f, m[1] + m[5]);
+}
 // v shifted by N lanes inside each row of 16 lanes (DPP row_shr: lane l takes
 // lane l - N, row_shl: lane l + N); a lane whose source lies outside the row
 // gets 0 (bound_ctrl), never stale register contents ...
@@ -227,11 +267,18 @@ struct ItemWalk {
 };
 __device__ __forceinline__ int itm_half(const ItemWalk& w, int il) { return w.at(il).half; }
 
+// UP25: the l-th live xi pair of an xi half (the upper half skips pairs 3-5, row 4)
+constexpr int up25_pair(int xh, int l) { return xh && l >= 3 ? l + 3 : l; }
+
 // UP: the Upsample conv, conv3x3 of the nearest-x2 upsampled source (WO / 2)^2:
 // the window rows 4ty-1 .. 4ty+4 of the upsampled image are source rows 2ty-1,
 // 2ty, 2ty, 2ty+1, 2ty+1, 2ty+2 and a lane's two columns one source column, so
-// a producer lane loads 4 source values instead of 12 (36 of the 144
-// multiplies per 4x4 output tile, against 64 for the sub-pixel direct kernel)
+// a producer lane loads 4 source values instead of 12.  UP has its own point
+// set (bt6u below; the route's WinoRoute::up_points packs U with its G), whose
+// V has a zero row and column for every such window: with XS = 2 (UP25) the 11
+// dead xi are neither produced, loaded nor multiplied -- 25 of the 144
+// multiplies per 4x4 output tile, against 64 for the sub-pixel direct kernel;
+// XS = 1 keeps all 36 (its dead ones are exact zeros)
 // XS = 2: each co block's 36 xi are split over two MFMA waves (xi 0-17 / 18-35:
 // Winograd rows 0-2 / 3-5) -- two MFMA waves per SIMD hide each other's
 // operand-read and issue stalls; each computes the partial output transform
@@ -268,6 +315,9 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
   constexpr int TS = TPR * TPR;        // tiles per sample (a multiple of 16)
   constexpr int WS = UP ? WO / 2 : WO; // source width
   constexpr int HWS = WS * WS;
+  // the Upsample conv on the xi-split kernel: the 11 xi of V's zero row and
+  // column (bt6u) are neither produced, loaded nor multiplied
+  constexpr bool UP25 = UP && XS == 2;
   static_assert(TS % 16 == 0 && TPR <= 16, "a 16-tile block is whole tile rows of one sample");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -434,9 +484,16 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
       }
       m[0] = m[0] * f32x2{pad[set].x, pad[set].x};
       m[5] = m[5] * f32x2{pad[set].y, pad[set].y};
-      bt6p(m, act2[ab]);
+      if constexpr (UP) bt6pu<UP25>(m, act2[ab]);
+      else bt6p(m, act2[ab]);
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
+        if constexpr (UP25) {
+          if (i == 4) {
+            actn[ab][i] = 0.f;
+            continue;
+          }
+        }
         const float give = h ? act2[ab][i].y : act2[ab][i].x;
         const float nb = __int_as_float(__builtin_amdgcn_ds_bpermute(nbaddr, __float_as_int(give)));
         actn[ab][i] = nb * pad[set].z;
@@ -466,8 +523,13 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         cx[r] = m.x;
         cy[r] = m.y;
       }
-      bt6(cx, act[ab][0]);
-      bt6(cy, act[ab][1]);
+      if constexpr (UP) {
+        bt6u<UP25>(cx, act[ab][0]);
+        bt6u<UP25>(cy, act[ab][1]);
+      } else {
+        bt6(cx, act[ab][0]);
+        bt6(cy, act[ab][1]);
+      }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
         const float give = h ? act[ab][1][i] : act[ab][0][i];
@@ -508,7 +570,12 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 #pragma unroll
       for (int aa = 0; aa < 3; ++aa) {
         float vv[6];
-        bt6(row[aa], vv);
+        if constexpr (UP) bt6u<UP25>(row[aa], vv);
+        else bt6(row[aa], vv);
+        if constexpr (UP25) {
+          // V row 4 (the upper half's aa = 1) is dead: nothing reads it
+          if (aa == 1 && h) continue;
+        }
 #pragma unroll
         for (int jp = 0; jp < 6; jp += 2)
           *reinterpret_cast<f32x2*>(o + (aa * 3 + jp / 2) * 128) = f32x2{vv[jp], vv[jp + 1]};
@@ -709,14 +776,16 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         f32x2 m[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) m[j] = f32x2{acc[6 * i + j][2 * pp], acc[6 * i + j][2 * pp + 1]};
-        at6(m, P[i]);
+        if constexpr (UP) at6u(m, P[i]);
+        else at6(m, P[i]);
       }
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         f32x2 col[6], yc[4];
 #pragma unroll
         for (int i = 0; i < 6; ++i) col[i] = P[i][x];
-        at6(col, yc);
+        if constexpr (UP) at6u(col, yc);
+        else at6(col, yc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           y[2 * pp][r][x] = yc[r].x;
@@ -830,7 +899,12 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
   };
   if (nloc > 0) {
 #pragma unroll
-    for (int p = 0; p < NP; ++p) u_load(ub[0], p);
+    for (int p = 0; p < NP; ++p) {
+      if constexpr (UP25) {
+        if (xh && p / 3 == 1) continue;        // (row 4: dead)
+      }
+      u_load(ub[0], p);
+    }
     u_advance();
   }
   if constexpr (GNC) {
@@ -878,12 +952,114 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
       if (p == NP - 1) u_advance();
     }
   };
+  // UP25: the chunk of one xi half (XH a constant: the halves differ).  Row 4
+  // is dead, so the upper half runs pairs 0-2 and 6-8 only; column 4 is dead,
+  // so a row's third pair issues the MFMA of its second xi only
+  auto chunk2u = [&](auto xhc, const float* vs) {
+    constexpr int XH = decltype(xhc)::value;
+    constexpr int NL = XH ? NP - 3 : NP;       // live pairs
+    constexpr int PD = WINO4S_PD;
+    f32x2 rb[PD + 1];
+#pragma unroll
+    for (int q = 0; q < PD; ++q) rb[q] = *reinterpret_cast<const f32x2*>(vs + (XH * NP + up25_pair(XH, q)) * 128);
+#pragma unroll
+    for (int q = 0; q < 2 * NL; ++q) {
+      const int st = q / NL, p = up25_pair(XH, q % NL);
+      const int qn = q + PD;
+      if (qn < 2 * NL)
+        rb[qn % (PD + 1)] =
+            *reinterpret_cast<const f32x2*>(vs + (qn / NL) * VKS + (XH * NP + up25_pair(XH, qn % NL)) * 128);
+      const int r = q % (PD + 1);
+      const f32x2 u = st == 0 ? ub[0][p] : ub[1][p];
+      const bool both = p % 3 != 2;
+      if (both) acc[2 * p] = __builtin_amdgcn_mfma_f32_16x16x4f32(u.x, rb[r].x, acc[2 * p], 0, 0, 0);
+      acc[2 * p + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(u.y, rb[r].y, acc[2 * p + 1], 0, 0, 0);
+      if (st == 0) u_load(ub[1], p);
+      else u_load(ub[0], p);
+      if (qn < 2 * NL) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      if (both) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      else __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      if (q % NL == NL - 1) u_advance();
+    }
+  };
   for (int il = 0; il < nloc; ++il) {
 #pragma unroll
     for (int x = 0; x < 2 * NP; ++x) acc[x] = f32x4{};
     f32x2 own[4][4];     // this wave's partial Y of its channel pair (pp = xh): [row][col]
+    // UP25: the partial output transform of one xi half.  Rows 0-2 are the
+    // points 0, 1, 1/2; rows 3-5 the points -1/2, -1 (dead: no products) and inf
+    auto tail_u = [&](auto xhc) {
+      constexpr int XH = decltype(xhc)::value;
+#pragma unroll
+      for (int pp = 0; pp < 2; ++pp) {
+        if (pp) __builtin_amdgcn_sched_barrier(0);   // (one channel pair at a time: registers)
+        f32x2 P[3][4], Y[4][4];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if (XH && i == 1) continue;
+          f32x2 m[6];
+#pragma unroll
+          for (int j = 0; j < 6; ++j)
+            if (j != 4) m[j] = f32x2{acc[6 * i + j][2 * pp], acc[6 * i + j][2 * pp + 1]};
+          m[4] = f32x2{0.f, 0.f};
+          at6u(m, P[i]);
+        }
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+          if constexpr (XH == 0) {
+            Y[0][x] = P[0][x] + (P[1][x] + P[2][x]);
+            Y[1][x] = fmac(P[2][x], 0.5f, P[1][x]);
+            Y[2][x] = fmac(P[2][x], 0.25f, P[1][x]);
+            Y[3][x] = fmac(P[2][x], 0.125f, P[1][x]);
+          } else {
+            Y[0][x] = P[0][x];
+            Y[1][x] = P[0][x] * f32x2{-0.5f, -0.5f};
+            Y[2][x] = P[0][x] * f32x2{0.25f, 0.25f};
+            Y[3][x] = fmac(P[0][x], -0.125f, P[2][x]);
+          }
+        }
+        if (pp == XH) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int x = 0; x < 4; ++x) own[r][x] = Y[r][x];
+        } else {
+          float* xw = xbuf + ((cb * 2 + (XH ^ 1)) * 8) * 256 + lane * 4;
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int x = 0; x < 4; x += 2)
+              *reinterpret_cast<f32x4*>(xw + (r * 2 + x / 2) * 256) =
+                  f32x4{Y[r][x].x, Y[r][x].y, Y[r][x + 1].x, Y[r][x + 1].y};
+        }
+      }
+    };
     if (il < 8) W4S_STAMP(3 + 3 * il);
     unsigned rpf[2] = {0u, 0u};   // the residual prefetch's destinations (kept until the epilogue)
+    // UP25: the item's chunks once per xi half with the half a constant -- the
+    // halves' chunks differ (no residual prefetch here: WINO4S_RPF is a
+    // prefetch only, and off)
+    auto kloop_u = [&](auto xhc) {
+      for (int k = 0; k < nchunk; ++k) {
+        const int g = il * nchunk + k;
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        chunk2u(xhc, vbuf + (g & 1) * V_FL + ln * 2);
+#pragma unroll
+        for (int x = 0; x < 2 * NP; ++x)
+          if (x % 6 != 4) asm volatile("" : "+v"(acc[x]));
+        if (k == nchunk - 1) tail_u(xhc);
+        __syncthreads();   // (B)
+#ifdef WINO4S_STAMP
+        if (g < 32) W4S_STAMP(28 + g);
+#endif
+      }
+    };
+    if constexpr (UP25) {
+      if (xh == 0) kloop_u(std::integral_constant<int, 0>{});
+      else kloop_u(std::integral_constant<int, 1>{});
+    } else {
     for (int k = 0; k < nchunk; ++k) {
       const int g = il * nchunk + k;
       int ln;
@@ -960,6 +1136,7 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 #ifdef WINO4S_STAMP
       if (g < 32) W4S_STAMP(28 + g);
 #endif
+    }
     }
     if (il < 8) W4S_STAMP(4 + 3 * il);
     // ---- finish this wave's channel pair: own partial + the partner's

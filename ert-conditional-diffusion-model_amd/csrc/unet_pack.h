@@ -84,15 +84,26 @@ __device__ __forceinline__ float pack_conv_up_elem(const float* __restrict__ w, 
 // points {0, 1, -1, 1/2, -2, inf}.  Thread j enumerates the packing's
 // (co, ci) in its own index order, so consecutive lanes write consecutive
 // floats of every xi.
-// F(4x4): j = [cog][chunk][cb 4][kk 4][c16 16]; writes 18 float2 (xi pairs)
+// F(4x4): j = [cog][chunk][cb 4][kk 4][c16 16]; writes 18 float2 (xi pairs).
+// A layer routed to WinoRoute::F4S_UP (WinoRoute::up_points) is packed with
+// the Upsample point set's G and read by that kernel only.
 __device__ __forceinline__ void pack_wino4_tile(const float* __restrict__ w, int cin, int cout, int nchunk,
-                                                size_t j, bool flipT, float* __restrict__ dst) {
-  constexpr double GD[6][3] = {{1.0, 0.0, 0.0},
-                               {1.0 / 3, 1.0 / 3, 1.0 / 3},
-                               {-1.0 / 3, 1.0 / 3, -1.0 / 3},
-                               {-16.0 / 15, -8.0 / 15, -4.0 / 15},
-                               {1.0 / 15, -2.0 / 15, 4.0 / 15},
-                               {0.0, 0.0, 1.0}};
+                                                size_t j, bool flipT, float* __restrict__ dst,
+                                                bool up = false) {
+  constexpr double GD_S1[6][3] = {{1.0, 0.0, 0.0},
+                                  {1.0 / 3, 1.0 / 3, 1.0 / 3},
+                                  {-1.0 / 3, 1.0 / 3, -1.0 / 3},
+                                  {-16.0 / 15, -8.0 / 15, -4.0 / 15},
+                                  {1.0 / 15, -2.0 / 15, 4.0 / 15},
+                                  {0.0, 0.0, 1.0}};
+  // up: the Upsample conv's points {0, 1, 1/2, -1/2, -1, inf} (unet_conv_wino4s.hip, bt6u)
+  constexpr double GD_UP[6][3] = {{1.0, 0.0, 0.0},
+                                  {2.0 / 3, 2.0 / 3, 2.0 / 3},
+                                  {-8.0 / 3, -4.0 / 3, -2.0 / 3},
+                                  {-8.0 / 3, 4.0 / 3, -2.0 / 3},
+                                  {2.0 / 3, -2.0 / 3, 2.0 / 3},
+                                  {0.0, 0.0, 1.0}};
+  const double (&GD)[6][3] = up ? GD_UP : GD_S1;
   const int c16 = (int)(j & 15);
   const int kk = (int)((j >> 4) & 3);
   const int cb = (int)((j >> 6) & 3);

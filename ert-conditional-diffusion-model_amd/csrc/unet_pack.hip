@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const ertd_pack_desc* _
     case ERTD_PACK_DIRECT: q.dst[i] = pack_conv_elem(q.w, q.cin, q.cout, q.ks, q.nchunk, i, q.flip != 0); break;
     case ERTD_PACK_UP: q.dst[i] = pack_conv_up_elem(q.w, q.cin, q.cout, q.nchunk, (size_t)q.total / 4, i); break;
     case ERTD_PACK_WINO: pack_wino_tile(q.w, q.cin, q.cout, q.nchunk, i, q.flip != 0, q.dst); break;
-    default: pack_wino4_tile(q.w, q.cin, q.cout, q.nchunk, i, q.flip != 0, q.dst); break;
+    default: pack_wino4_tile(q.w, q.cin, q.cout, q.nchunk, i, q.flip != 0, q.dst, q.reserved == 1); break;
   }
 }
 

@@ -84,7 +84,7 @@ def unet_flops(image=64, ch=64, ch_mult: Sequence[int] = (1, 2, 4), num_res=2, a
     level's kernel depends on the batch; None = the F(2x2) count there)."""
     cfg = make_config(image, ch, ch_mult, num_res, attn, groups)
     layout = param_layout(cfg)
-    conv = dense = ups = ups4 = wino = wino4 = 0
+    conv = dense = ups = ups4 = ups25 = wino = wino4 = 0
     # spatial size per conv: walk the layout names
     res_of = {}
     r = image
@@ -122,7 +122,12 @@ def unet_flops(image=64, ch=64, ch_mult: Sequence[int] = (1, 2, 4), num_res=2, a
                 # wino4s_up_ok, else 4 sub-pixel 2x2 convs (4 of the 9 taps)
                 if shape[1] % 8 == 0 and shape[0] % 64 == 0 and hw in (32, 64) or \
                         (hw == 16 and shape[1] % 8 == 0 and shape[0] % 64 == 0 and f4_items_fill(hw, shape[0])):
-                    ups4 += f
+                    # Cin >= 16 (the xi-split kernel): the 11 products of V's zero
+                    # row and column are skipped, 25 of 144 multiplies
+                    if shape[1] >= 16:
+                        ups25 += f
+                    else:
+                        ups4 += f
                 else:
                     ups += f
             # ResBlock 3x3 convs the fp32 Winograd kernels take: F(4x4,3x3) at
@@ -143,12 +148,14 @@ def unet_flops(image=64, ch=64, ch_mult: Sequence[int] = (1, 2, 4), num_res=2, a
         attn_f = 2 * 2 * N * N * C
     enc = 6_308_736 + 14_426_112 + 2 * 64 * 128   # the reference's condition encoder
     # executed MFMA work: F(4x4,3x3) 36 multiplies per 4x4 outputs instead of
-    # 144, F(2x2,3x3) 16 per 2x2 instead of 36, sub-pixel Upsample 4 of 9 taps
+    # 144 (25 for the Upsample convs on the xi-split kernel), F(2x2,3x3) 16 per
+    # 2x2 instead of 36, sub-pixel Upsample 4 of 9 taps
     return {"conv": conv, "attention": attn_f, "dense": dense, "condition_encoder": enc,
             "total": conv + attn_f + dense + enc,
-            "conv_winograd": wino + wino4 + ups4,
-            "conv_winograd_f4": wino4 + ups4,
-            "conv_executed_fp32": conv - ups * 5 // 9 - wino * 5 // 9 - (wino4 + ups4) * 3 // 4}
+            "conv_winograd": wino + wino4 + ups4 + ups25,
+            "conv_winograd_f4": wino4 + ups4 + ups25,
+            "conv_executed_fp32": conv - ups * 5 // 9 - wino * 5 // 9 - (wino4 + ups4) * 3 // 4
+                                  - ups25 * 119 // 144}
 
 
 class ConditionalUNet(nn.Module):

@@ -764,7 +764,8 @@ typedef struct {
   int flip;            /* 1: the input-gradient conv's transposed, flipped weight */
   int nchunk;          /* K chunks of the layout                                  */
   int block0;          /* first 256-thread block (ertd_conv_pack_batch_prepare)   */
-  int reserved;
+  int reserved;        /* set by the *_pack_desc queries (ERTD_PACK_WINO4: 1 = the      */
+                       /* Upsample conv's point set); pass it on unchanged              */
 } ertd_pack_desc;
 int ertd_conv2d_pack_desc(int Cin, int Ca, int Cout, int ks, int mode, int precision, int B, int H,
                           const float* w, void* ws, ertd_pack_desc* out);
