@@ -52,17 +52,6 @@ struct GnPartArgs {
   float2* mr;            // optional (B, groups) {mean, rstd}
 };
 
-// The consumer GroupNorm's finalize folded into the producing conv: the MFMA
-// waves store their partials write-through, every finished item adds one to
-// its sample's counter, and once its items are done, workgroup w waits for
-// the counts of samples w, w + grid, ... and finalizes them -- no finalize launch.
-struct GnFold {
-  GnPartArgs g;          // g.pa = the conv's own partials (ConvArgs::gnp), g.out the consumer's {scale, shift}
-  unsigned* cnt;         // (B) arrival counters: zero before the launch, left zero by it
-  int target;            // arrivals (items) per sample
-  int B;                 // samples: workgroup w finalizes samples w, w + grid, ...
-};
-
 struct ConvArgs {
   const float* srcA;     // (B, Ca, Hs, Ws)  channels [0, Ca)
   const float* srcB;     // (B, Cb, Hs, Ws)  channels [Ca, Ca+Cb) (skip concat) or null
@@ -91,10 +80,6 @@ struct ConvArgs {
                          // kernel emits none and gnp must be null)
   int split;             // bf16 kernels: 1 = split-bf16 operands (hi + lo planes: weights
                          // packed with split = true, images of conv_bf16_image_bytes(.., true))
-  GnFold fold;           // fp32 Winograd F(4x4) kernels with gnp: the next GroupNorm's finalize
-                         // (fold.cnt null: none; WinoRoute::fold_ok says where it is taken)
-  unsigned* zero_words;  // conv_in: zero these zero_n words (the fold counters of the walk)
-  int zero_n;
   GnPartArgs gnc;        // fp32 Winograd F(4x4) consumers (gnc.pa non-null): the input's
                          // GroupNorm finalize in the conv's own prologue (wino_gnc_ok):
                          // the {scale, shift} of the sample the workgroup runs are merged from
@@ -127,8 +112,6 @@ struct WinoRoute {
   size_t kbuf_floats = 0;
   int items = 0, grid = 0;   // tile items (both halves of a split) and workgroups of the launch
   int gn_parts = 0;       // GroupNorm partials per (sample, channel) the epilogue emits (0: none)
-  bool fold_ok = false;   // the kernel takes ConvArgs::fold (diagnostic builds)
-  int fold_target = 0;    // F4S / F4S_UP: items per sample = the fold's arrivals (GnFold::target)
   int pack_kind = ERTD_PACK_DIRECT;   // the weight packing the launch reads (ERTD_PACK_*)
   bool up_points = false; // ERTD_PACK_WINO4 in the Upsample point set (F4S_UP: the kernel's
                           // transforms and the packing's G are chosen together, here)
@@ -158,19 +141,6 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
-// ---- the GroupNorm finalize folded into the producing conv (GnFold) --------------
-// write-through (agent-coherent) float2 store / load of the partials: the
-// arriving waves of other workgroups (other XCDs' L2s) see them
-__device__ __forceinline__ void st_f2_wt(float2* p, float2 v) {
-  unsigned* u = reinterpret_cast<unsigned*>(p);
-  __hip_atomic_store(u, __float_as_uint(v.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(u + 1, __float_as_uint(v.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float2 ld_f2_wt(const float2* p) {
-  const unsigned* u = reinterpret_cast<const unsigned*>(p);
-  return make_float2(__uint_as_float(__hip_atomic_load(u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)),
-                     __uint_as_float(__hip_atomic_load(u + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-}
 // GroupNorm statistics of one group from its parts' {sum, M2 about the part
 // mean}, in float64 and a fixed order -- two passes over the parts:
 //   S = sum_k sum_k,  mean = S / N,  M2 = sum_k (M2_k + n_k (sum_k / n_k - mean)^2)
@@ -179,13 +149,11 @@ __device__ __forceinline__ float2 ld_f2_wt(const float2* p) {
 // parts k = sub + GN_LPG i (channel-major, A then B) in ascending i, and the
 // lanes' totals meet in an xor butterfly (a + b == b + a, so every lane ends
 // with the same bits).  gn_finalize_kernel, the consumer-side finalize of the
-// F(4x4) conv (gn_group_finalize_regs) and the diagnostic fold all run this
-// arithmetic, so a group's {scale, shift} has the same bits whichever runs it.
+// F(4x4) conv (gn_group_finalize_regs) both run this arithmetic, so a group's
+// {scale, shift} has the same bits whichever runs it.
 // (Rounds 3-5 merged the parts with Chan's pairwise update: a float64
 // division per part and per butterfly level.)
-#ifndef FOLD_BATCH
-#define FOLD_BATCH 4   // parts loaded per round trip and lane
-#endif
+constexpr int GN_PARTS_PER_TRIP = 4;   // parts loaded per lane and round trip (gn_group_finalize)
 constexpr int GN_LPG = 16;
 struct GnGroupGeom {
   int c0, itemsA, items;          // first channel, parts of tensor A, all parts (0: dead lane group)
@@ -234,16 +202,13 @@ __device__ __forceinline__ float2 gn_mean_rstd(double mean, double Q, double N) 
   var = var > 0.0 ? var : 0.0;
   return make_float2((float)mean, (float)(1.0 / sqrt(var + GN_EPS)));
 }
-template <bool WT>
 __device__ __forceinline__ float2 gn_ld_part(const GnGroupGeom& q, int k) {
-  return k < q.itemsA ? (WT ? ld_f2_wt(q.pa + k) : q.pa[k]) : q.pb[k - q.itemsA];
+  return k < q.itemsA ? q.pa[k] : q.pb[k - q.itemsA];
 }
 // Groups [part * ceil(G / nparts), ...) of sample b finalized by the calling
-// wave, parts streamed FOLD_BATCH per lane and round trip (the second pass
-// re-reads them: L2-hot).  WT: the A partials were written in this launch
-// (write-through loads).  orow: where {scale, shift} of sample b's channels go
+// wave, parts streamed GN_PARTS_PER_TRIP per lane and round trip (the second pass
+// re-reads them: L2-hot).  orow: where {scale, shift} of sample b's channels go
 // (null: g.out + b * C).
-template <bool WT>
 __device__ __forceinline__ void gn_group_finalize(const GnPartArgs& g, int b, int lane, int part,
                                                   int nparts, float2* orow = nullptr) {
   const int G = g.groups, C = g.Ca + g.Cb, cpg = C / G;
@@ -260,29 +225,29 @@ __device__ __forceinline__ void gn_group_finalize(const GnPartArgs& g, int b, in
     const int gi = gfirst + gl;
     const GnGroupGeom q = gn_group_geom(g, b, gi, live);
     double S = 0.0;
-    for (int k0 = sub; k0 < q.items; k0 += FOLD_BATCH * LPG) {
-      float2 v[FOLD_BATCH];
+    for (int k0 = sub; k0 < q.items; k0 += GN_PARTS_PER_TRIP * LPG) {
+      float2 v[GN_PARTS_PER_TRIP];
 #pragma unroll
-      for (int j = 0; j < FOLD_BATCH; ++j) {
+      for (int j = 0; j < GN_PARTS_PER_TRIP; ++j) {
         const int k = k0 + j * LPG;
-        v[j] = k < q.items ? gn_ld_part<WT>(q, k) : make_float2(0.f, 0.f);
+        v[j] = k < q.items ? gn_ld_part(q, k) : make_float2(0.f, 0.f);
       }
 #pragma unroll
-      for (int j = 0; j < FOLD_BATCH; ++j)
+      for (int j = 0; j < GN_PARTS_PER_TRIP; ++j)
         if (k0 + j * LPG < q.items) S += (double)v[j].x;
     }
     S = gn_lpg_sum(S);
     const double mean = S / N;
     double Q = 0.0;
-    for (int k0 = sub; k0 < q.items; k0 += FOLD_BATCH * LPG) {
-      float2 v[FOLD_BATCH];
+    for (int k0 = sub; k0 < q.items; k0 += GN_PARTS_PER_TRIP * LPG) {
+      float2 v[GN_PARTS_PER_TRIP];
 #pragma unroll
-      for (int j = 0; j < FOLD_BATCH; ++j) {
+      for (int j = 0; j < GN_PARTS_PER_TRIP; ++j) {
         const int k = k0 + j * LPG;
-        v[j] = k < q.items ? gn_ld_part<WT>(q, k) : make_float2(0.f, 0.f);
+        v[j] = k < q.items ? gn_ld_part(q, k) : make_float2(0.f, 0.f);
       }
 #pragma unroll
-      for (int j = 0; j < FOLD_BATCH; ++j) {
+      for (int j = 0; j < GN_PARTS_PER_TRIP; ++j) {
         const int k = k0 + j * LPG;
         if (k < q.items) Q += k < q.itemsA ? gn_part_q(v[j], na, ina, mean) : gn_part_q(v[j], nb, inb, mean);
       }
@@ -326,7 +291,7 @@ __device__ __forceinline__ void gn_group_finalize_regs(const GnPartArgs& g, cons
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
       const int kk = sub + LPG * k;
-      v[j][k] = kk < q[j].items ? gn_ld_part<false>(q[j], kk) : make_float2(0.f, 0.f);
+      v[j][k] = kk < q[j].items ? gn_ld_part(q[j], kk) : make_float2(0.f, 0.f);
     }
     const bool ch = live[j] && sub < cpg;
     ga[j] = ch ? g.gamma[q[j].c0 + sub] : 0.f;
@@ -356,22 +321,6 @@ __device__ __forceinline__ void gn_group_finalize_regs(const GnPartArgs& g, cons
     }
   }
 }
-// called by every MFMA wave of a producing conv once per item, after its
-// partials of sample b are stored with st_f2_wt (whole wave active): the
-// item's last wave (an LDS count over the nw MFMA waves) adds the item's one
-// arrival to the sample's counter -- without waiting for the atomic's return
-// (same-address device atomics serialize: the count is read at the tail)
-__device__ __forceinline__ void gn_fold_item_done(const GnFold& f, int b, int* lds_cnt, int nw, int lane) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  int old = 0;
-  if (lane == 0) old = atomicAdd(lds_cnt, 1);
-  old = __builtin_amdgcn_readfirstlane(old);
-  if (old == nw - 1 && lane == 0) {
-    *lds_cnt = 0;
-    (void)__hip_atomic_fetch_add(f.cnt + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
 // The kernel launch_conv runs for (ks, mode, act, a, B) and the persistent
 // launch's geometry: the one decision launch_conv switches on, and what
 // ertd_conv2d_route_info reports (pointers of `a` are tested for null, never
@@ -429,12 +378,11 @@ hipError_t launch_pack_conv_wino(const float* w, int cin, int cout, float* dst, 
 // unet_conv1x1.hip): per-sample GEMM, weights and input by LDS-DMA
 bool conv1x1_ok(const ConvArgs& a, int act, int B);
 hipError_t launch_conv1x1(const ConvArgs& a, int B, hipStream_t s);
-// the 1x1 skip convs as a batched GEMM on 32x32x2 fp32 MFMAs (unet_skip_gemm.hip)
+// the 1x1 skip convs as a batched GEMM on split-bf16 MFMAs (unet_skip_gemm.hip)
 bool skip_gemm_ok(const ConvArgs& a, int ks, int mode, int act, int B);
-// geom non-null: nothing is launched; *geom = the launch's kernel, tile and
-// persistent geometry (the launchers' own ntiles and occupancy-derived cap)
+// geom non-null: nothing is launched; *geom = the launch's tile and
+// persistent geometry (the launcher's own ntiles and occupancy-derived cap)
 struct SkipGemmGeom {
-  bool split = false;        // the split-bf16 kernel (else the fp32 one)
   int mt = 0, nt = 0;        // tile: output channels x pixels
   int items = 0, grid = 0;   // tiles and workgroups
 };

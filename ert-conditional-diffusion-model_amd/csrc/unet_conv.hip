@@ -516,7 +516,7 @@ static bool direct_ok(int ks, int mode, int act) {
 }
 
 // The dispatch, in the order of precedence: conv_out, conv_in, the Winograd
-// route, the direct 3x3 kernels, the sub-pixel Upsample conv, the skip GEMMs,
+// route, the direct 3x3 kernels, the sub-pixel Upsample conv, the skip GEMM,
 // the LDS-DMA 1x1 kernel, the direct 1x1 kernels.
 ConvDispatch conv_dispatch(int ks, int mode, int act, const ConvArgs& a, int B) {
   ConvDispatch d;
@@ -547,7 +547,7 @@ ConvDispatch conv_dispatch(int ks, int mode, int act, const ConvArgs& a, int B) 
   } else if (skip_gemm_ok(a, ks, mode, act, B)) {
     SkipGemmGeom g;
     if (launch_skip_gemm(a, B, nullptr, &g) != hipSuccess) return d;
-    d.kernel = g.split ? ERTD_ROUTE_SKIP_GEMM_SPLIT : ERTD_ROUTE_SKIP_GEMM;
+    d.kernel = ERTD_ROUTE_SKIP_GEMM_SPLIT;
     d.items = g.items;
     d.grid = g.grid;
   } else if (ks == 1 && mode == MODE_S1 && act == ACT_NONE && conv1x1_ok(a, act, B)) {
@@ -563,7 +563,6 @@ hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipS
   if (d.kernel < 0) return hipErrorInvalidValue;
   const WinoRoute& r = d.route;
   if (a.gnp && conv_gn_parts(ks, mode, act, a, r) == 0) return hipErrorInvalidValue;
-  if (a.fold.cnt && (!a.gnp || a.fold.g.pa != a.gnp || !r.fold_ok)) return hipErrorInvalidValue;
   if (a.gnc.pa && (act == ACT_NONE || !wino_gnc_ok(r, a.Cin, a.Wo, a.gnc))) return hipErrorInvalidValue;
   switch (d.kernel) {
     case ERTD_ROUTE_CONV_OUT: return launch_conv_out(act, a, B, PK_F32, s);
@@ -583,7 +582,6 @@ hipError_t launch_conv(int ks, int mode, int act, const ConvArgs& a, int B, hipS
         default: return hipErrorInvalidValue;
       }
     }
-    case ERTD_ROUTE_SKIP_GEMM:
     case ERTD_ROUTE_SKIP_GEMM_SPLIT: return launch_skip_gemm(a, B, s);
     case ERTD_ROUTE_CONV1X1: return launch_conv1x1(a, B, s);
     default: break;

@@ -518,8 +518,6 @@ __global__ __launch_bounds__(256) void conv_in_kernel(ConvArgs a) {
             : PK == PK_F32 ? packed_w0_f32(a.wpk, co, tap) : packed_w0_bf16(a.wpk, co, tap, PK == PK_SPLIT);
   }
   if (tid < 64) bl[tid] = (a.bias && cg + tid < Cout) ? a.bias[cg + tid] : 0.f;
-  if (a.zero_words && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)   // the walk's GroupNorm-fold counters
-    for (int i = tid; i < a.zero_n; i += 256) a.zero_words[i] = 0u;
   const int p = part * 256 + 4 * lane;
   const int y = p / WO, x0 = p - y * WO;
   const float* src = a.srcA + (size_t)b * HW;

@@ -720,15 +720,13 @@ WinoRoute wino_route(int mode, int act, int Cin, int Ca, int Cout, int Wo, int B
   } else {
     return r;
   }
-  const bool f2 = r.kernel == WinoRoute::F2, s = r.kernel == WinoRoute::F4S || r.kernel == WinoRoute::F4S_UP;
+  const bool f2 = r.kernel == WinoRoute::F2;
   r.ksplit = split ? 2 : 1;
   r.kbuf_floats = split ? (size_t)B * Cout * Wo * Wo : 0;
   r.items = base * r.ksplit;
   r.grid = r.items < cus ? r.items : cus;
   // (no partials from a split layer: a separate pass sums the halves after the epilogue)
   r.gn_parts = split ? 0 : (f2 ? (Wo / 2) * (Wo / 2) / 32 : t4 / 16);
-  r.fold_ok = s && !split;   // every MFMA wave of an unsplit item arrives once
-  r.fold_target = s ? t4 / 16 * ncog : 0;
   r.pack_kind = f2 ? ERTD_PACK_WINO : ERTD_PACK_WINO4;
   r.up_points = r.kernel == WinoRoute::F4S_UP;
   return r;

@@ -54,7 +54,6 @@ namespace unet {
 
 namespace {
 
-constexpr int NMW = 4;                        // co blocks (MFMA waves at XS = 1, one per SIMD)
 constexpr int NPW = 4;                        // producer waves
 constexpr int CCH = 8;                        // input channels per chunk (2 MFMA k-steps)
 constexpr int NX = 36;
@@ -80,15 +79,8 @@ constexpr int GNC_TAB = 4096;                 //   table entries (item x channel
 #ifndef WINO4S_XCDMAX
 #define WINO4S_XCDMAX 2                       // ... for layers of at most this many co groups
 #endif
-#ifndef WINO4S_PACK
-#define WINO4S_PACK 1                         // producer stage on packed fp32 pairs
-#endif
 #ifndef WINO4S_HALO
-#define WINO4S_HALO 1                         // 16x16 / 32x32 producers: own rows once, halo rows by DPP (needs WINO4S_PACK)
-#endif
-#ifndef WINO4S_RPF
-#define WINO4S_RPF 0                          // residual L2 prefetch this many chunks before the epilogue
-                                              // (0: none; 2: 250.2 vs 252.2 steps/s U2 B=64, same box)
+#define WINO4S_HALO 1                         // 16x16 / 32x32 producers: own rows once, halo rows by DPP
 #endif
 // Ablations for a diagnostic build only (tools/build_variant.sh ... -DWINO4S_ABL=n;
 // results WRONG, never in the shipped library): bit 0 the producers skip the
@@ -196,24 +188,6 @@ __device__ __forceinline__ void at6(const f32x2 (&m)[6], f32x2 (&y)[4]) {
   y[3] = fmac(m[3], 0.125f, fmac(m[4], -8.f, d + m[5]));
 }
 
-// the GroupNorm fold's finalizes, after the MFMA waves' last item (the
-// producer waves have exited: the barrier counts the MFMA waves): samples
-// bid, bid + grid, ... -- wave 0 waits for the sample's item count (all
-// workgroups are resident: one per CU, grid <= CUs) and re-arms the counter,
-// then every MFMA wave finalizes its share of the sample's groups
-__device__ __forceinline__ void wino4s_fold_tail(const GnFold& f, int lane, int wave, int nmw) {
-  for (int b = blockIdx.x; b < f.B; b += gridDim.x) {
-    if (wave == 0 && lane == 0) {
-      const unsigned* c = f.cnt + b;
-      while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned)f.target)
-        __builtin_amdgcn_s_sleep(2);
-      __hip_atomic_store(f.cnt + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    gn_group_finalize<true>(f.g, b, lane, wave, nmw);
-  }
-}
-
 #ifdef WINO4S_STAMP
 // Diagnostic build only (tools/wino4s_stamps.py): per-wave s_memtime stamps of
 // workgroups 0..255, stored by lane 0 with vector stores.  Per wave (S4_SPW
@@ -260,12 +234,11 @@ __device__ __forceinline__ Item item_of(int it, int ncog, int ksp) {
   return r;
 }
 
-// a workgroup's items in walk order: item base + il stride
+// a workgroup's items in walk order: items bid, bid + G, ...
 struct ItemWalk {
-  int base, stride, ncog, ksp;
-  __device__ __forceinline__ Item at(int il) const { return item_of(base + il * stride, ncog, ksp); }
+  int bid, G, ncog, ksp;
+  __device__ __forceinline__ Item at(int il) const { return item_of(bid + il * G, ncog, ksp); }
 };
-__device__ __forceinline__ int itm_half(const ItemWalk& w, int il) { return w.at(il).half; }
 
 // UP25: the l-th live xi pair of an xi half (the upper half skips pairs 3-5, row 4)
 constexpr int up25_pair(int xh, int l) { return xh && l >= 3 ? l + 3 : l; }
@@ -284,10 +257,6 @@ constexpr int up25_pair(int xh, int l) { return xh && l >= 3 ? l + 3 : l; }
 // operand-read and issue stalls; each computes the partial output transform
 // of its rows, the halves are exchanged through LDS across the item's last
 // barrier, and each wave finishes two of the lane's four channels
-// FOLD (diagnostic builds only, ERTD_UNET_GNFOLD): the GroupNorm fold's
-// write-through partial stores, arrival counts and finalize tail.  The shipped
-// instantiation (FOLD = false) has none of it: no static LDS word in front of
-// the dynamic V buffers, no per-item branches.
 // GNC: the input's GroupNorm finalize runs in this kernel's prologue
 // (ConvArgs::gnc, wino_gnc_ok): before the first chunk the 8 MFMA waves
 // -- idle until the producers stage chunk 0 -- merge the partials of every
@@ -296,19 +265,11 @@ constexpr int up25_pair(int xh, int l) { return xh && l >= 3 ? l + 3 : l; }
 // bits, with all loads issued first), while the producers' first input loads
 // are in flight; the producers read the table instead of ConvArgs::gn.  One
 // launch (3.3 us of the step graph, measured) per GroupNorm fewer.
-// cw > 0 (diagnostic A/B only): contiguous walk -- workgroup bid runs items
-// bid * cw .. bid * cw + cw - 1 (nitems == grid * cw); 0: items bid, bid + grid, ...
-template <int WO, int ACT, bool UP, int XS, bool FOLD, bool GNC>
-__global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvArgs a, int nitems, int ksp, int cw) {
-  static_assert(!GNC || (XS == 2 && !UP && ACT != ACT_NONE && !FOLD), "GNC: the xi-split GN+act kernel");
+template <int WO, int ACT, bool UP, int XS, bool GNC>
+__global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvArgs a, int nitems, int ksp) {
+  static_assert(!GNC || (XS == 2 && !UP && ACT != ACT_NONE), "GNC: the xi-split GN+act kernel");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* vbuf = smem;                  // [2][V_FL]
-  int* fold_items = nullptr;           // GroupNorm fold: MFMA waves done with the current item
-  if constexpr (FOLD) {
-    __shared__ int fold_lds;
-    fold_items = &fold_lds;
-    if (threadIdx.x == 0) fold_lds = 0;
-  }
 
   constexpr int TPR = WO / 4;
   constexpr int HW = WO * WO;
@@ -340,9 +301,8 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
   const int G = gridDim.x;
   const int bid = (WINO4S_XCD && G % 8 == 0 && ncog <= WINO4S_XCDMAX)
                       ? (int)(blockIdx.x % 8) * (G / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const ItemWalk wk = cw ? ItemWalk{bid * cw, 1, ncog, ksp} : ItemWalk{bid, G, ncog, ksp};
-  const int nloc = cw ? (bid * cw < nitems ? min(cw, nitems - bid * cw) : 0)
-                      : (bid < nitems ? (nitems - bid + G - 1) / G : 0);
+  const ItemWalk wk{bid, G, ncog, ksp};
+  const int nloc = bid < nitems ? (nitems - bid + G - 1) / G : 0;
   float2* const gtab = reinterpret_cast<float2*>(smem + 2 * V_FL + 4 * 2 * 8 * 256);   // GNC: [item][Cin]
   const int gtot = nloc * nchunk;
 
@@ -363,7 +323,7 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
     // activates its own rows once and takes the halo rows by DPP.  At 32x32
     // the item's upper tile row has no lane above and the lower none below:
     // every lane runs one extra row, window row 0 (t < 8) or 5 (t >= 8).
-    constexpr bool HALO = WINO4S_HALO && WINO4S_PACK && !UP && TPR <= 8;
+    constexpr bool HALO = WINO4S_HALO && !UP && TPR <= 8;
     constexpr int NWR = HALO ? (TPR == 8 ? 5 : 4) : 6;   // rows loaded per slot
     float2 raw[NRS][NWR];
     float2 gnv[NRS];
@@ -437,14 +397,13 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         }
       }
     };
-    // act[ab][c][i]: row i of B^T d for local column c (window columns 1+2h,
-    // 2+2h and the outer one): the lane transforms its own two columns and takes
-    // the outer column's transform from the neighbouring tile's lane (B^T is
-    // linear, so transforming before the exchange skips the third column's bt6)
-#if WINO4S_PACK
-    // the lane's two own columns as one packed pair through GroupNorm, SiLU,
-    // the row padding and the column transform (v_pk_* on f32x2: the same fma /
-    // mul / add per element as the scalar form, so the same bits); exp and rcp
+    // Row i of B^T d for the lane's window columns 1+2h, 2+2h and the outer
+    // one: the lane transforms its own two columns and takes the outer column's
+    // transform from the neighbouring tile's lane (B^T is linear, so
+    // transforming before the exchange skips the third column's bt6).  The two
+    // own columns go as one packed pair through GroupNorm, SiLU, the row
+    // padding and the column transform (v_pk_* on f32x2: the same fma / mul /
+    // add per element as the scalar form, so the same bits); exp and rcp
     // have no packed form.  act2[ab][i] = transformed row i of (col a, col b),
     // actn[ab][i] = that of the outer column (from the neighbour lane)
     f32x2 act2[2][6];
@@ -499,60 +458,14 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         actn[ab][i] = nb * pad[set].z;
       }
     };
-#else
-    float act[2][3][6];
-    auto act_stage = [&](const int set, const int ab) {
-      if constexpr (GNC) gnv[set] = gtab[gch[set]];
-      float cx[6], cy[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        float2 m = raw[set][r];
-        if constexpr (ACT != ACT_NONE) {
-          m.x = __builtin_fmaf(m.x, gnv[set].x, gnv[set].y);
-          m.y = __builtin_fmaf(m.y, gnv[set].x, gnv[set].y);
-          if constexpr (ACT == ACT_GN_SILU) {
-            m.x = m.x * __builtin_amdgcn_rcpf(1.0f + __expf(-m.x));
-            m.y = m.y * __builtin_amdgcn_rcpf(1.0f + __expf(-m.y));
-          }
-        }
-        if (r == 0 || r == 5) {
-          const float fy = r == 0 ? pad[set].x : pad[set].y;
-          m.x *= fy;
-          m.y *= fy;
-        }
-        cx[r] = m.x;
-        cy[r] = m.y;
-      }
-      if constexpr (UP) {
-        bt6u<UP25>(cx, act[ab][0]);
-        bt6u<UP25>(cy, act[ab][1]);
-      } else {
-        bt6(cx, act[ab][0]);
-        bt6(cy, act[ab][1]);
-      }
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const float give = h ? act[ab][1][i] : act[ab][0][i];
-        const float nb = __int_as_float(__builtin_amdgcn_ds_bpermute(nbaddr, __float_as_int(give)));
-        act[ab][2][i] = nb * pad[set].z;
-      }
-    };
-#endif
     auto tr_stage = [&](const int ab, float* vb) {
       float w[6][3];
-#if WINO4S_PACK
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
         w[i][0] = act2[ab][i].x;
         w[i][1] = act2[ab][i].y;
         w[i][2] = actn[ab][i];
       }
-#else
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) w[i][c] = act[ab][c][i];
-#endif
       // rows 0-2 to the lower half (h = 0), 3-5 to the upper: the rows of 16
       // lanes pair (0,1), (2,3) -- afterwards row[a][j] is row 3h+a of window column j
       float row[3][6];
@@ -846,11 +759,9 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float2* d = a.gnp + ((size_t)smpl * a.Cout + co0 + i) * np + part;
-          if constexpr (FOLD) st_f2_wt(d, pr[i]);
-          else *d = pr[i];
+          *d = pr[i];
         }
       }
-      if constexpr (FOLD) gn_fold_item_done(a.fold, smpl, fold_items, NMW, ln);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -859,7 +770,6 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, y[i][r]), ro, vo,
                                                i * HW * 4 + r * WO * 4, 0);
   }
-  if constexpr (FOLD) wino4s_fold_tail(a.fold, lane, wave, NMW);
   } else {
   // =================== MFMA waves, xi split over two waves ===================
   constexpr int NP = 9;                        // xi pairs per wave
@@ -1036,10 +946,8 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
       }
     };
     if (il < 8) W4S_STAMP(3 + 3 * il);
-    unsigned rpf[2] = {0u, 0u};   // the residual prefetch's destinations (kept until the epilogue)
     // UP25: the item's chunks once per xi half with the half a constant -- the
-    // halves' chunks differ (no residual prefetch here: WINO4S_RPF is a
-    // prefetch only, and off)
+    // halves' chunks differ
     auto kloop_u = [&](auto xhc) {
       for (int k = 0; k < nchunk; ++k) {
         const int g = il * nchunk + k;
@@ -1064,26 +972,6 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
       const int g = il * nchunk + k;
       int ln;
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-#if WINO4S_RPF
-      // the epilogue's residual tile into L2 WINO4S_RPF chunks ahead (its HBM
-      // latency was the epilogue's critical path): one dword per 16-B segment of
-      // tiles 0, 8 / 4, 12 of each (channel, row) -- every 128-B line of the
-      // wave's residual rows at 64x64, 32x32 and 16x16
-      if (k == (nchunk > WINO4S_RPF ? nchunk - WINO4S_RPF : 0) && a.res && itm_half(wk, il) == 0) {
-        const Item pit = wk.at(il);
-        const int pflat = pit.blk * 16, psm = pflat / TS;
-        const int pco = pit.cog * 64 + cb * 16 + 4 * (ln >> 4) + 2 * xh + ((ln >> 3) & 1);
-        const int pr = (ln >> 1) & 3;
-        const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(a.res) + (size_t)psm * a.Cout * HW, (short)0, (unsigned)(a.Cout * HW * 4), 0x00020000);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int ptg = pflat % TS + (ln & 1) * 8 + h * 4;
-          const int pty = ptg / TPR, ptx = ptg - pty * TPR;
-          rpf[h] = __builtin_amdgcn_raw_buffer_load_b32(rp, (pco * HW + (4 * pty + pr) * WO + 4 * ptx) * 4, 0, 0);
-        }
-      }
-#endif
       chunk2(vbuf + (g & 1) * V_FL + ln * 2);
 #pragma unroll
       for (int x = 0; x < 2 * NP; ++x) asm volatile("" : "+v"(acc[x]));
@@ -1196,7 +1084,6 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 #pragma unroll
         for (int r = 0; r < 4; ++r) y[i][r] = y[i][r] + rv[i][r];
     }
-    asm volatile("" ::"v"(rpf[0]), "v"(rpf[1]));   // (younger than the prefetch: it has landed)
     if (a.gnp && !part2) {
       float2 pr[2];
 #pragma unroll
@@ -1221,11 +1108,9 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           float2* d = a.gnp + ((size_t)smpl * a.Cout + co0 + i) * np + part;
-          if constexpr (FOLD) st_f2_wt(d, pr[i]);
-          else *d = pr[i];
+          *d = pr[i];
         }
       }
-      if constexpr (FOLD) gn_fold_item_done(a.fold, smpl, fold_items, 4 * XS, ln);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1236,7 +1121,6 @@ __global__ __launch_bounds__(64 * (4 * XS + NPW)) void conv_wino4s_kernel(ConvAr
     if (il < 8) W4S_STAMP(5 + 3 * il);
   }
   W4S_STAMP(27);
-  if constexpr (FOLD) wino4s_fold_tail(a.fold, lane, wave, 4 * XS);
   }
 
 }
@@ -1255,68 +1139,32 @@ extern "C" int ertd_diag_wino4s_stamps_clear() {
 }
 #endif
 
-// contiguous walk (items bid * cw ...), diagnostic builds only:
-// ERTD_WINO4S_CWALK=1 takes it for every xi-split layer that can.  Measured
-// (U2 B=64, same box): 249.4 -> 243.8 steps/s -- the strided walk keeps the
-// concurrently running items in a few samples (16 of 64 at 64x64), the
-// contiguous one spreads them over all 64 at a 1-MB sample stride
-static int wino4s_cwalk_env() {
-  static const int v = [] {
-    return ERTD_KNOB("WINO4S_CWALK", 0);
-  }();
-  return v;
-}
-
-// items per workgroup of the contiguous walk, or 0 where it does not apply:
-// the xi-split kernel (Cin >= 16) without a K split, items an exact multiple of
-// the grid, each workgroup's run inside one sample
-static int wino4s_cw_geom(int Cin, const WinoRoute& r) {
-  if (r.ksplit != 1 || wino4s_xs() != 2 || Cin < 16 || r.grid < 1 || r.items % r.grid) return 0;
-  const int cw = r.items / r.grid;
-  return r.fold_target % cw == 0 ? cw : 0;   // (fold_target: the items of one sample)
-}
-
 namespace {
-
-int wino4s_cwalk(const ConvArgs& a, const WinoRoute& r) {
-  if (wino4s_cwalk_env() == 0 || a.fold.cnt) return 0;
-  return wino4s_cw_geom(a.Cin, r);
-}
 
 template <int WO, int ACT, bool UP, int XS>
 hipError_t launch_wo4x(const ConvArgs& a, hipStream_t s, const WinoRoute& r) {
   constexpr size_t lds = WLDS + (XS == 2 ? (size_t)4 * 2 * 8 * 256 * sizeof(float) : 0);
   const int nitems = r.items, grid = r.grid, ksp = r.ksplit;
-  // the fold and the consumer-side finalize ride on unsplit items only (the
-  // latter's branch below returns before the pass that sums a split's halves);
-  // the single-wave variant has no split either
-  if (ksp != 1 && (a.gnc.pa || a.fold.cnt || XS != 2)) return hipErrorInvalidValue;
-  const int cw = wino4s_cwalk(a, r);
-#ifdef ERTD_DIAG
-  if (a.fold.cnt) {
-    static std::atomic<unsigned long long> attr{0};
-    set_max_lds_once((const void*)conv_wino4s_kernel<WO, ACT, UP, XS, true, false>, (int)lds, attr);
-    conv_wino4s_kernel<WO, ACT, UP, XS, true, false><<<grid, 64 * (4 * XS + NPW), lds, s>>>(a, nitems, ksp, cw);
-  } else
-#else
-  if (a.fold.cnt) return hipErrorInvalidValue;   // the fold is built into diagnostic libraries only
-#endif
+  // the consumer-side finalize rides on unsplit items only (its branch below
+  // returns before the pass that sums a split's halves); the single-wave
+  // variant has no split either
+  if (ksp != 1 && (a.gnc.pa || XS != 2)) return hipErrorInvalidValue;
   if constexpr (XS == 2 && !UP && ACT != ACT_NONE) {
     if (a.gnc.pa) {
       const int nlocmax = (nitems + grid - 1) / grid;
-      const size_t ldsg = lds + (size_t)(cw ? cw : nlocmax) * a.Cin * sizeof(float2);
+      const size_t ldsg = lds + (size_t)nlocmax * a.Cin * sizeof(float2);
       static std::atomic<unsigned long long> attr{0};
-      set_max_lds_once((const void*)conv_wino4s_kernel<WO, ACT, UP, XS, false, true>,
+      set_max_lds_once((const void*)conv_wino4s_kernel<WO, ACT, UP, XS, true>,
                        (int)(lds + GNC_TAB * sizeof(float2)), attr);
-      conv_wino4s_kernel<WO, ACT, UP, XS, false, true><<<grid, 64 * (4 * XS + NPW), ldsg, s>>>(a, nitems, ksp, cw);
+      conv_wino4s_kernel<WO, ACT, UP, XS, true><<<grid, 64 * (4 * XS + NPW), ldsg, s>>>(a, nitems, ksp);
       return hipGetLastError();
     }
   }
   if (a.gnc.pa) return hipErrorInvalidValue;
   {
     static std::atomic<unsigned long long> attr{0};
-    set_max_lds_once((const void*)conv_wino4s_kernel<WO, ACT, UP, XS, false, false>, (int)lds, attr);
-    conv_wino4s_kernel<WO, ACT, UP, XS, false, false><<<grid, 64 * (4 * XS + NPW), lds, s>>>(a, nitems, ksp, cw);
+    set_max_lds_once((const void*)conv_wino4s_kernel<WO, ACT, UP, XS, false>, (int)lds, attr);
+    conv_wino4s_kernel<WO, ACT, UP, XS, false><<<grid, 64 * (4 * XS + NPW), lds, s>>>(a, nitems, ksp);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || ksp == 1) return e;
@@ -1359,7 +1207,7 @@ bool wino_gnc_ok(const WinoRoute& r, int Cin, int Wo, const GnPartArgs& g) {
       (g.Cb > 0 && (!g.pb || g.npb < 1)) || g.HW != Wo * Wo || g.HW % g.npa ||
       (g.Cb > 0 && g.HW % g.npb))
     return false;
-  const int nloc = wino4s_cwalk_env() ? wino4s_cw_geom(Cin, r) : (r.items + r.grid - 1) / r.grid;
+  const int nloc = (r.items + r.grid - 1) / r.grid;
   const int cpg = Cin / g.groups;
   const int np = g.npa > g.npb ? g.npa : g.npb;
   if (env == 2 && nloc > 1) return false;   // (diagnostic: single-item workgroups only)

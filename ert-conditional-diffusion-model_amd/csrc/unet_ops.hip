@@ -147,7 +147,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 // One wave per (sample, GN_LPG-group chunk): unet.h gn_group_finalize (the
-// same arithmetic as the producing convs' GroupNorm fold): float64 Chan merge
+// same arithmetic as the F(4x4) conv's consumer-side finalize): float64 merge
 // of the parts {sum, M2 about the part mean} in a fixed order, var = M2 / N
 // (biased, as GroupNorm); {scale, shift} as gn_stats_kernel.
 __global__ __launch_bounds__(256) void gn_finalize_kernel(GnPartArgs a, int B) {
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(GnPartArgs a, int B) {
   const int wv = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (wv >= B * nparts) return;
   const int b = wv / nparts;
-  gn_group_finalize<false>(a, b, lane, wv - b * nparts, nparts);
+  gn_group_finalize(a, b, lane, wv - b * nparts, nparts);
 }
 
 #ifdef GN_FIN_TWICE

@@ -62,7 +62,7 @@ class RouteInfo(ctypes.Structure):
                 ("grid", ctypes.c_int), ("gn_parts", ctypes.c_int)]
 
 
-# ERTD_ROUTE_* in value order
+# ERTD_ROUTE_* in value order ("skip_gemm", 5, is reserved: no longer reported)
 ROUTE_KERNELS = ("direct", "conv_in", "conv_out", "up", "conv1x1", "skip_gemm", "skip_gemm_split",
                  "f2", "f4", "f4s", "f4s_up", "bf16")
 

@@ -487,7 +487,7 @@ int ertd_conv2d_run_gn(const float* x, int Ca, const float* x2, int Cb, int B, i
  *   a geometry ertd_conv2d rejects.
  *   kernel   ERTD_ROUTE_*;
  *   ksplit   2: a Winograd layer's input channels run as two half-items, else 1;
- *   items, grid   persistent kernels (the Winograd convs, the skip GEMMs): work
+ *   items, grid   persistent kernels (the Winograd convs, the skip GEMM): work
  *            items of the launch and its workgroups; workgroup g runs items g,
  *            g + grid, ... (in the F4S kernel's XCD-aware order where it takes
  *            it), so with items > grid and items % grid != 0 neighbouring
@@ -506,7 +506,7 @@ int ertd_conv2d_run_gn(const float* x, int Ca, const float* x2, int Cb, int B, i
 #define ERTD_ROUTE_CONV_OUT 2         /* Cout = 1 3x3                               */
 #define ERTD_ROUTE_UP 3               /* sub-pixel Upsample conv                    */
 #define ERTD_ROUTE_CONV1X1 4          /* 1x1, LDS-DMA                               */
-#define ERTD_ROUTE_SKIP_GEMM 5        /* 1x1 batched GEMM, fp32 MFMA                */
+#define ERTD_ROUTE_SKIP_GEMM 5        /* reserved (the fp32 MFMA GEMM): not reported */
 #define ERTD_ROUTE_SKIP_GEMM_SPLIT 6  /* 1x1 batched GEMM, split-bf16 MFMA          */
 #define ERTD_ROUTE_F2 7               /* Winograd F(2x2,3x3)                        */
 #define ERTD_ROUTE_F4 8               /* Winograd F(4x4,3x3), weights in LDS        */

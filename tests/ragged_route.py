@@ -1,6 +1,6 @@
 """Batches at which a persistent conv kernel's work items do not divide its grid.
 
-The fp32 Winograd convs and the skip GEMMs are persistent: workgroup g of G
+The fp32 Winograd convs and the skip GEMM are persistent: workgroup g of G
 runs items g, g + G, ...; with items > G and items % G != 0 neighbouring
 workgroups run different numbers of items.  Which batch produces that walk
 depends on the device's CU count and on the dispatch, so the tests ask the

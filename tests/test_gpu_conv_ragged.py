@@ -1,11 +1,11 @@
 """The persistent fp32 conv kernels where their work items do not divide the grid.
 
 conv_wino4s_kernel (F4S, F4S_UP), conv_wino4_kernel (F4), conv_wino_kernel
-(F2) and the two skip GEMMs launch one workgroup per CU (or a few) that walks
+(F2) and the skip GEMM launch one workgroup per CU (or a few) that walks
 items bid, bid + G, ...  A workgroup carries state across its item boundaries
 (the producers' prefetch of the next item's first chunk, the xi halves'
 exchange buffer, the GroupNorm table indexed by the local item number, the
-skip GEMMs' chunk ring), and with items > G, items % G != 0 neighbouring
+skip GEMM's chunk ring), and with items > G, items % G != 0 neighbouring
 workgroups run different numbers of items: some have a next item, some do not.
 The batch that produces this walk depends on the CU count, so every case asks
 the library's route query (ertdiff.unet.conv2d_route) for the smallest such
@@ -149,24 +149,6 @@ def test_conv2d_ragged(case, cuda_dev):
     if case.startswith("j_"):
         assert B % 2 == 0   # a 32-tile block holds two samples
     _check(case, sh, B, r, cuda_dev, seed=100 + 10 * list(RAGGED).index(case))
-
-
-def test_conv2d_ragged_skip_gemm_fp32(cuda_dev):
-    """(n) the fp32 skip GEMM kernel: whichever 1x1 shape the split-bf16 kernel's
-    tile choice declines and the fp32 one takes, at a ragged batch."""
-    for Cout in (64, 128, 192, 256, 320):
-        for H in (16, 32, 64):
-            for Cin in (32, 96, 256):
-                sh = Shape(Cin, 0, Cout, H, ks=1, res=True)
-                B = find_B(sh, lambda r: r.kernel == "skip_gemm" and r.items > r.grid > 0 and r.items % r.grid,
-                           cuda_dev)
-                if B is not None:
-                    r = route(sh, B, cuda_dev)
-                    assert_ragged(r, "skip_gemm")
-                    _check("n_skip_fp32", sh, B, r, cuda_dev, seed=300)
-                    return
-    pytest.skip("no 1x1 shape reaches skip_gemm (fp32 MFMA) with B <= 192: the split-bf16 kernel takes every "
-                "shape the fp32 kernel's tiles divide")
 
 
 def test_conv2d_f4s_grid_not_multiple_of_8(cuda_dev):

@@ -26,10 +26,8 @@ zeroed by launch_zero_words on the stream before the chain (capi.hip,
 enqueue_sample; its spins are bounded and report through the status word);
 train.hip's fin_cnt arrival counters are zeroed by the step's first kernel
 (enc_train_kernel, item 0) and re-armed by the last arriver -- no wait; the
-U-Net walk's fold_cnt (the one unbounded wait, wino4s_fold_tail) is zeroed by
-the walk's conv_in launch, and a fold is planned only after that launch
-(cnt_zeroed in unet_capi.hip); its step-counter slot is set by the sampler's
-head before any step reads it.  Draws (draw = 1) are formed in registers and
+U-Net walk has no device-side wait at all, and its step-counter slot is set by
+the sampler's head before any step reads it.  Draws (draw = 1) are formed in registers and
 stored: t is never read back from the caller's buffer."""
 import ctypes
 import functools
